@@ -8,7 +8,7 @@ workload (default, --config c3 = BASELINE configs[2], the largest single-GPU
          config and c4's per-GPU shard): 1,024 independently seeded 44.1 kHz
          stereo 128 kbps CBR streams x 1,024 frames per GPU (seeds
          1 + 1024 rank .. 1024 (rank + 1), synthetic Layer III writer); the c2
-         stream (1 x 10,000 frames, granule-parallel) is timed beside it.
+         stream (1 x 10,000 frames, granule-parallel) is timed beside it (--full).
          --config c2 / c5: those configs as the headline.
 scaling: weak -- every rank decodes its own stream(s); no data-path collective
          (value = frames of all ranks / max-over-ranks time).  With N > 1 the
@@ -17,7 +17,19 @@ scaling: weak -- every rank decodes its own stream(s); no data-path collective
          buffer), timed and reported separately under "gather" (value stays
          the kernel-only number); --no-gather skips it.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  One process per
+Launch: python bench.py [--gpus N --steps K --warmup W].  A plain run does what
+the headline figure needs and no more: it builds the workload, runs W untimed
+and K timed steps of the headline plan, writes --dump-outputs if asked and
+prints the result line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the workload and the roofline of the timed kernel's own time).
+--full adds every other leg: the other mode, the oracle parity and CPU
+baselines, the shader-clock probe, the loud-input, bitstream, polyphase and c2
+legs, the profile-derived roofline fields, the N > 1 gather and the host-memory
+report (the --no-* options below trim a --full run).  --dump-outputs DIR
+writes a fixed, seeded sample of the PCM of the last timed step as
+DIR/pcm.npy (float32 [k][576][2]) beside the sampled granule numbers
+(DIR/pcm_granule_index.npy, float64); the input is seeded, so two builds run
+with the same arguments can be compared sample for sample.  One process per
 GPU: under torch.distributed.run (WORLD_SIZE must equal N), or, with no
 launcher and N > 1, bench.py starts `torch.distributed.run --nproc-per-node N`
 itself as a child process before anything touches the GPU and passes its
@@ -66,6 +78,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10,
                     help="untimed steps first (the clock takes ~6 launches of c3 to settle)")
     ap.add_argument("--config", choices=["c2", "c3", "c5"], default="c3")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline (other mode, oracle parity, CPU baselines, clock probe, "
+                         "loud-input / bitstream / polyphase / c2 legs, profile-derived fields, gather, host memory)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a seeded sample of the last step's PCM to DIR/pcm.npy "
+                         "(float32) and the sampled granule numbers to DIR/pcm_granule_index.npy (float64)")
     ap.add_argument("--c5-copies", type=int, default=256,
                     help="c5: copies of each reference sample stream per GPU")
     ap.add_argument("--chunk", type=int, default=0, help="granules per chunk (0 = auto)")
@@ -93,7 +111,11 @@ def parse():
                     help="c3 loud-input leg: shares of granules made loud (about 1.7x as many end up hot)")
     ap.add_argument("--parity-streams", type=int, default=128,
                     help="c3: streams whose PCM is checked against the oracle (all host threads)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline alone
+        args.single_mode = args.no_cpu_baseline = args.no_gather = args.no_bitstream = True
+        args.no_pipelined = args.no_polyphase = args.no_c2 = args.no_hot = True
+    return args
 
 
 def build_workload(cfg, rank, seed_base=1, c5_copies=256):
@@ -914,6 +936,28 @@ def host_memory_report(world, coll_dev):
                     "(host_scan.cpp) and decoder pools come on top (DESIGN.md section 13)"}
 
 
+DUMP_GRANULES = 8192  # x 1152 samples x 4 B = 37.7 MB of float32 (the dump stays under 64 MB)
+
+
+def dump_outputs(out_dir, d_pcm, n_gran, rank, world):
+    """--dump-outputs: the PCM the timed plan wrote in its last step, as
+    float32 [k][576][2] (the int16 values, exact in float32): every granule
+    when there are at most DUMP_GRANULES, else a fixed sample of that many
+    (seed 0, ascending), with the sampled granule numbers beside it.  Rank r
+    of an N > 1 run writes pcm_rank<r>.npy."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    if n_gran <= DUMP_GRANULES:
+        idx = np.arange(n_gran, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n_gran, DUMP_GRANULES, replace=False)).astype(np.int64)
+    rows = d_pcm.view(n_gran, 1152).index_select(0, torch.from_numpy(idx).to(d_pcm.device))
+    pcm = rows.cpu().numpy().astype(np.float32).reshape(-1, 576, 2)
+    tag = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(out_dir, "pcm%s.npy" % tag), pcm)
+    np.save(os.path.join(out_dir, "pcm_granule_index%s.npy" % tag), idx.astype(np.float64))
+
+
 def launch_ranks(n):
     """`bench.py --gpus N` with no launcher around it: start N ranks with
     torch.distributed.run as a CHILD process (never exec: this process must not
@@ -1003,16 +1047,20 @@ def main():
                                          args.warmup, stream, world, dev)
         t_max = mdist.max_over_ranks(wall, device=coll_dev)
         frames_all = n_frames * world
+        if mode_name == args.mode and args.dump_outputs:
+            dump_outputs(args.dump_outputs, d_pcm, n_gran, rank, world)
         return {"value": frames_all * args.steps / t_max, "ms_per_step": 1000.0 * t_max / args.steps,
                 "kernel_ms": kern_ms, "chunks": pinfo["chunks"], "halo_granules": pinfo["halo_granules"],
-                # (rank 0) the timed output, for the parity check below
-                "pcm": d_pcm.cpu().numpy().reshape(-1, 576, 2) if rank == 0 else None}
+                # (rank 0, --full) the timed output, for the parity check below
+                "pcm": d_pcm.cpu().numpy().reshape(-1, 576, 2) if rank == 0 and args.full else None}
 
     # the clock the headline kernel runs at on this box, measured on its own
     # launches just before the timed region (they double as warm-up; the
     # profile passes keep taking the last --steps launches as the timed ones)
-    box_clock = clock_leg(mp3g, streams, d_g, d_c, d_pcm,
-                          mp3g.MODE_FAST if args.mode == "fast" else mp3g.MODE_EXACT, args.chunk, local, dev)
+    box_clock = None
+    if args.full:
+        box_clock = clock_leg(mp3g, streams, d_g, d_c, d_pcm,
+                              mp3g.MODE_FAST if args.mode == "fast" else mp3g.MODE_EXACT, args.chunk, local, dev)
     modes = [args.mode] + ([] if args.single_mode else [m for m in MODES if m != args.mode])
     res = {m: measure(m) for m in modes}
     main_res = res[args.mode]
@@ -1020,7 +1068,7 @@ def main():
     # the fast kernel's hot-granule fallback on the timed input itself: one
     # more launch with the plan's counters
     hot_timed = None
-    if "fast" in res and hasattr(mp3g.lib(), "mp3g_plan_hot_stats"):
+    if args.full and "fast" in res and hasattr(mp3g.lib(), "mp3g_plan_hot_stats"):
         hp_ = mp3g.Plan(streams, granules_per_chunk=args.chunk, mode=mp3g.MODE_FAST | mp3g.FLAG_HOT_STATS,
                         device=local)
         hp_.execute(d_g, d_c, d_pcm, stream=h)
@@ -1079,9 +1127,40 @@ def main():
     gather = None
     if dist.is_initialized() and not args.no_gather:
         gather = gather_leg(args, rank, world, dev, d_pcm, n_gran, mdist)
-    host_mem = host_memory_report(world, coll_dev)
+    host_mem = host_memory_report(world, coll_dev) if args.full else None
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        # a plain run: the headline and what follows from its own time
+        kern_ms = main_res["kernel_ms"]
+        achieved = n_gran * BYTES_PER_GRANULE / (kern_ms * 1e-3) / 1e9
+        out = {
+            "metric": METRIC,
+            "value": round(main_res["value"], 1),
+            "unit": "frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(main_res["ms_per_step"], 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "full": False,
+            "config": dict(cfg_info, mode=MODES[args.mode][0],
+                           parallelism=f"{world} independent ranks (stream sharding, no data-path collective)",
+                           granules_per_gpu=int(n_gran), chunks=main_res["chunks"],
+                           halo_granules=main_res["halo_granules"]),
+            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
+                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5),
+                         "kernel": MODES[args.mode][1], "kernel_ms": round(kern_ms, 4),
+                         "algorithmic_bytes_per_frame": BYTES_PER_FRAME,
+                         "algorithmic_bytes_per_launch": n_gran * BYTES_PER_GRANULE},
+            "dump_outputs": args.dump_outputs,
+            "note": "max |dPCM| against the oracle and every other leg: --full",
+        }
+        print(json.dumps(out), flush=True)
+    if rank == 0 and args.full:
         kern_ms = main_res["kernel_ms"]
         achieved = n_gran * BYTES_PER_GRANULE / (kern_ms * 1e-3) / 1e9
         traffic, traffic_src, traffic_sha = profiled_traffic(args.config, MODES[args.mode][1])

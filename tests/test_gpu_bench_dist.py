@@ -32,7 +32,7 @@ def _free_port():
 def test_bench_two_ranks_gloo(config):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           os.path.join(REPO, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1",
            "--config", config, "--backend", "gloo", "--single-mode", "--no-bitstream", "--no-polyphase"]
     env = dict(os.environ, OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO, env=env)
@@ -54,7 +54,7 @@ def test_bench_two_ranks_gloo(config):
 def test_bench_gpus_flag_launches_ranks():
     """Plain `bench.py --gpus 2` (no launcher): bench.py starts the two ranks
     itself; gloo, so both share cuda:0."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1",
            "--config", "c2", "--backend", "gloo", "--single-mode", "--no-bitstream", "--no-polyphase"]
     env = dict(os.environ, OMP_NUM_THREADS="4")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -72,7 +72,7 @@ def test_bench_gpus_flag_launches_ranks():
 def test_bench_one_rank_rccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           os.path.join(REPO, "bench.py"), "--gpus", "1", "--full", "--steps", "2", "--warmup", "1",
            "--config", "c2", "--backend", "nccl", "--single-mode", "--no-bitstream", "--no-polyphase",
            "--cpu-repeats", "1"]
     env = dict(os.environ, OMP_NUM_THREADS="4")
@@ -92,7 +92,7 @@ def test_bench_pinned_budget_guard():
     budget too small for the bitstream leg's pinned buffers, the PCIe pass
     and the pipelined drop-in are skipped and say so, the device leg and its
     oracle parity still run, and 2 gloo ranks gather into pageable memory."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1",
            "--config", "c2", "--backend", "gloo", "--single-mode", "--no-polyphase", "--no-hot"]
     env = dict(os.environ, OMP_NUM_THREADS="4", MP3G_BENCH_PINNED_GB="0.01")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):

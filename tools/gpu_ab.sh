@@ -33,7 +33,7 @@ for rep in $(seq 1 $REPS); do
     for lib in "$@"; do
       steps=10; [ $cfg = c2 ] && steps=200
       log=gpurun_out/ab_${lib%.so}_${cfg}_$rep.log
-      MP3G_LIB=$L/$lib timeout -k 10 300 python bench.py --config $cfg --steps $steps --warmup 3 $BARGS \
+      MP3G_LIB=$L/$lib timeout -k 10 300 python bench.py --full --config $cfg --steps $steps --warmup 3 $BARGS \
         > $log 2>&1 || { tail -5 $log; exit 1; }
       tail -1 $log | python -c "
 import json, sys

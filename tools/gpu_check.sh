@@ -5,6 +5,7 @@ set -u
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 T=${1:-r04}; shift || true
+set -- --full "$@"  # every leg of the bench (max |dPCM| comes from its oracle parity)
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > gpurun_out/${T}_pytest.log 2>&1 || { tail -30 gpurun_out/${T}_pytest.log; exit 1; }
 tail -3 gpurun_out/${T}_pytest.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${T}_smoke.log 2>&1 || { tail -20 gpurun_out/${T}_smoke.log; exit 1; }

@@ -20,7 +20,7 @@ mkdir -p gpurun_out
 for rep in $(seq 1 $REPS); do
   for lib in "$@"; do
     log=gpurun_out/hotab_${lib%.so}_$rep
-    MP3G_LIB=$PWD/go-mp3_amd/mp3g/$lib timeout -k 10 300 python bench.py --config c3 --steps 10 --warmup 5 --single-mode \
+    MP3G_LIB=$PWD/go-mp3_amd/mp3g/$lib timeout -k 10 300 python bench.py --full --config c3 --steps 10 --warmup 5 --single-mode \
       --no-cpu-baseline --no-bitstream --no-polyphase --hot-fracs $FRACS > $log.json 2> $log.err || { tail -5 $log.err; exit 1; }
     python - $log.json $lib <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ set -u
 TAG=$1; CFG=$2; shift 2; EXTRA="$*"
 export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT
-B="bench.py --config $CFG --steps 3 --warmup 1 --no-cpu-baseline $EXTRA"
+B="bench.py --full --config $CFG --steps 3 --warmup 1 --no-cpu-baseline $EXTRA"
 run() { local name=$1; shift; echo "== $name" >> $OUT/prof_${TAG}.log
   timeout -k 10 300 "$@" >> $OUT/prof_${TAG}.log 2>&1; local rc=$?; echo "== $name rc=$rc" | tee -a $OUT/prof_${TAG}.log
   if [ $rc -ge 124 ]; then exit $rc; fi; }

@@ -11,7 +11,7 @@ set -u
 TAG=$1; CFG=$2; shift 2; EXTRA="$*"
 export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT
-H="bench.py --config $CFG --steps 5 --warmup 3 --single-mode --no-cpu-baseline --no-bitstream --no-polyphase --no-c2 --no-pipelined --no-hot $EXTRA"
+H="bench.py --full --config $CFG --steps 5 --warmup 3 --single-mode --no-cpu-baseline --no-bitstream --no-polyphase --no-c2 --no-pipelined --no-hot $EXTRA"
 run() {
   local name=$1; shift
   echo "== $name: $*" >> $OUT/prof_${TAG}.log

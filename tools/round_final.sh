@@ -16,6 +16,7 @@ set -u
 export TMPDIR=/tmp
 T=${1:-r06}
 mkdir -p gpurun_out
+LOGS=$_  # (the log folder made above)
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > gpurun_out/${T}m_pytest.log 2>&1 || { tail -30 gpurun_out/${T}m_pytest.log; exit 1; }
 tail -3 gpurun_out/${T}m_pytest.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${T}m_smoke.log 2>&1 || { tail -20 gpurun_out/${T}m_smoke.log; exit 1; }
@@ -27,10 +28,10 @@ python3 tools/summarize_calib.py gpurun_out/prof_${T}_fetchcal gpurun_out/${T}_f
 bash tools/summarize_round.sh $T > gpurun_out/summarize_${T}.log 2>&1 || { tail -20 gpurun_out/summarize_${T}.log; exit 1; }
 mkdir -p gpurun_out/profiles_$T
 cp profiles/${T}_c3_*.json profiles/${T}_c3_*.csv profiles/${T}_flop_calib.json profiles/${T}_fetch_calib.json gpurun_out/profiles_$T/
-timeout -k 10 400 python bench.py > gpurun_out/${T}m_bench.json 2> gpurun_out/${T}m_bench.err || { tail -20 gpurun_out/${T}m_bench.err; exit 1; }
-python - "$T" <<'PY'
+timeout -k 10 400 python bench.py --full > $LOGS/${T}m_bench.json 2> $LOGS/${T}m_bench.err || { tail -20 $LOGS/${T}m_bench.err; exit 1; }
+python - "$LOGS/${T}m_bench.json" <<'PY'
 import json, sys
-d = json.loads(open(f'gpurun_out/{sys.argv[1]}m_bench.json').read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d['roofline']
 p = r.get('profile') or {}
 print(d['value'], d['ms_per_step'], r['kernel_ms'], r['frac'], d.get('max_dpcm_lsb'), 'same build:', r.get('traffic_same_build'),
