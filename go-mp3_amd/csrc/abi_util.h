@@ -27,4 +27,8 @@ struct ZoneScratch;  // kernels.h
 int plan_launch(uint32_t mode, const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
                 const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out, int16_t* d_pcm,
                 const ZoneScratch* zones, hipStream_t stream);
+// The same with an output format (MP3G_OUT_*; plan_launch is MP3G_OUT_S16).
+int plan_launch_out(uint32_t mode, const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
+                    const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out, void* d_out,
+                    uint32_t out_format, const ZoneScratch* zones, hipStream_t stream);
 }  // namespace mp3g

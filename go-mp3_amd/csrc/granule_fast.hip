@@ -933,6 +933,82 @@ __device__ __forceinline__ void store_pcm(int16_t* pcm, uint32_t g, bool out, co
     __builtin_amdgcn_raw_buffer_store_b32(pk[p], rp, 4 * (32 * (2 * p + hi) + k), 0, MP3G_PCM_STORE_AUX);
 }
 
+// ---- float32 output (MP3G_OUT_F32 / MP3G_OUT_F32_PLANAR) ----
+// The window leaves lane (ch, k) slots 2p and 2p + 1 of output k in acc2[p]
+// (sum * 32767): the float sample is the s16 sample's clamp without the
+// truncation, scaled by 2^-15 (exact), so trunc(f * 32768) is the s16 sample.
+// A float store from this layout needs no cross-lane pack.  Mono: channel 0's
+// values go to the channel-1 lanes (v_permlane32_swap of a value with itself
+// hands every lane the low half's), which then write them to the other
+// channel / plane (frame.go:671-678).
+#ifndef MP3G_F32_STORE_SWAP
+#define MP3G_F32_STORE_SWAP 0  // (A/B) interleaved: swap + one 64-bit (L, R) store per slot pair
+#endif
+__device__ __forceinline__ void pack_pcm(const f2 acc2[9], int nch, float pf[18]) {
+#pragma unroll
+  for (int p = 0; p < 9; p++) {
+    pf[2 * p] = __builtin_amdgcn_fmed3f(acc2[p].x, -32767.0f, 32767.0f) * (1.0f / 32768.0f);
+    pf[2 * p + 1] = __builtin_amdgcn_fmed3f(acc2[p].y, -32767.0f, 32767.0f) * (1.0f / 32768.0f);
+  }
+  if (nch != 2) {  // (wave-uniform)
+#pragma unroll
+    for (int i = 0; i < 18; i++) {
+      const uint32_t u = __builtin_bit_cast(uint32_t, pf[i]);
+      pf[i] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_permlane32_swap(u, u, false, false)[0]);
+    }
+  }
+}
+
+// Where a chunk's stream lies (planar output: ChunkDesc::stream_first / stream_n).
+struct StreamGeom {
+  uint32_t first, n;
+};
+
+// Float samples of granule g, one dword per lane and slot, non-temporal like
+// the s16 stores and issued for replayed granules too (no records).
+//   F32:    float [g][32 slot + k][ch]: a store covers 256 contiguous bytes;
+//           the resource spans the granule's block (4,608 B).
+//   planar: plane(ch) + 576 (g - first) + 32 slot + k: two 128-B runs; the
+//           resource starts at the granule's place in plane 0 and ends with
+//           its place in plane 1 (the lane offset n * 2304 + 2300 stays below
+//           2^31: MP3G_PLANAR_MAX_GRANULES).
+template <int kFmt>
+__device__ __forceinline__ void store_pcm_f32(int16_t* pcm, StreamGeom sg, uint32_t g, bool out, const float pf[18],
+                                              int ch, int k) {
+  float* const o = reinterpret_cast<float*>(pcm);
+  if constexpr (kFmt == (int)MP3G_OUT_F32) {
+    const __amdgpu_buffer_rsrc_t rp =
+        __builtin_amdgcn_make_buffer_rsrc(o + (size_t)g * 1152, (short)0, out ? 2 * MP3G_PCM_BYTES_PER_GRANULE : 0, 0x00020000);
+#if MP3G_F32_STORE_SWAP
+    typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int p = 0; p < 9; p++) {
+      // as the s16 pack: lane i gets slot 2p's (L, R), lane 32 + i slot 2p + 1's
+      // (mono: pack_pcm has made both channels equal already)
+      const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, pf[2 * p]),
+                                                      __builtin_bit_cast(uint32_t, pf[2 * p + 1]), false, false);
+      const u2v v = {(uint32_t)r[0], (uint32_t)r[1]};
+      __builtin_amdgcn_raw_buffer_store_b64(v, rp, 8 * (32 * (2 * p + ch) + k), 0, MP3G_PCM_STORE_AUX);
+    }
+#else
+#pragma unroll
+    for (int sl = 0; sl < 18; sl++)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[sl]), rp, 8 * (32 * sl + k) + 4 * ch, 0,
+                                            MP3G_PCM_STORE_AUX);
+#endif
+  } else {
+    const uint32_t plane = sg.n * (uint32_t)MP3G_PCM_BYTES_PER_GRANULE;  // bytes of one plane
+    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
+        o + (size_t)sg.first * 1152 + (size_t)(g - sg.first) * MP3G_LINES, (short)0,
+        out ? (int)(plane + MP3G_PCM_BYTES_PER_GRANULE) : 0, 0x00020000);
+    const int base = (int)(ch ? plane : 0u) + 4 * k;
+#pragma unroll
+    for (int sl = 0; sl < 18; sl++)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[sl]), rp, base + 128 * sl, 0,
+                                            MP3G_PCM_STORE_AUX);
+  }
+}
+
 // Entry state of a replay start: overlap store in registers, V history as X
 // vectors, from the stream's state_in (init_in) or zero.  stp[q] =
 // (store[q], store[17-q]), each element times the frequency-inversion sign of
@@ -1074,7 +1150,9 @@ constexpr int kPhases = 8;
 // its work to the counters in aux (kHotCounters); a separate instantiation
 // because the counting alone cost the production kernel ~1.5 % (register
 // allocation).
-template <bool kStamp, bool kHotCount = false>
+// kFmt: the output format (MP3G_OUT_*), which only the window's store stage
+// reads: everything before it is the same instructions in every format.
+template <bool kStamp, bool kHotCount = false, int kFmt = (int)MP3G_OUT_S16>
 __global__ void __launch_bounds__(kLanes * kWaves, MP3G_FAST_WAVES_PER_SIMD)
 granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, const mp3g_granule* __restrict__ gran,
                     const int16_t* __restrict__ coef, const mp3g_state* __restrict__ state_in,
@@ -1205,43 +1283,67 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
   // (lanes of an absent channel compute values that are never stored; the
   // PCM stores are issued for replayed granules too, through a resource with
   // no records)
+  // the window sums of output k: acc2[p] = slots (2p, 2p + 1), times 32767
+  auto window_acc = [&](f2 (&acc2)[9]) {
+    float dw[16];
+    {
+      const float4* d4 = reinterpret_cast<const float4*>(&sh.dwin[k][0]);
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const float4 v = d4[q];
+        dw[4 * q] = v.x;
+        dw[4 * q + 1] = v.y;
+        dw[4 * q + 2] = v.z;
+        dw[4 * q + 3] = v.w;
+      }
+    }
+    // accumulator pair p = output slots (2p, 2p+1).  Tap 2t of the pair reads
+    // column a of rows (v, v+1) and tap 2t+1 column b of rows (v-1, v),
+    // v = 2p - 2t: every operand pair is two rows of one column, i.e. one
+    // ds_read2_b32 that lands as the packed operand, and each feeds up to 8
+    // accumulator pairs.
+    const f2* RA = reinterpret_cast<const f2*>(&s.ring[ch][pa][0]);
+    const float* RB = &s.ring[ch][pb][0];
+#pragma unroll
+    for (int p = 0; p < 9; p++) acc2[p] = bcast(0.0f);
+#pragma unroll
+    for (int v = -14; v <= 16; v += 2) {
+      const f2 A = RA[(kHist + v) / 2];  // slots (16+v, 17+v): 8-B aligned
+      const f2 B = {RB[kHist + v - 1], RB[kHist + v]};
+#pragma unroll
+      for (int t = 0; t < 8; t++) {
+        const int p = v / 2 + t;
+        if (p >= 0 && p < 9) {
+          acc2[p] = pfma(bcast(dw[2 * t]), A, acc2[p]);
+          acc2[p] = pfma(bcast(dw[2 * t + 1]), B, acc2[p]);
+        }
+      }
+    }
+  };
+  // (planar float output only: the stream's place, wave-uniform)
+  StreamGeom geom = {0u, 0u};
+  if constexpr (kFmt == (int)MP3G_OUT_F32_PLANAR)
+    geom = StreamGeom{(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)cd.stream_first),
+                      (uint32_t)__builtin_amdgcn_readfirstlane(cd.stream_n)};
   auto window_store = [&](uint32_t g, bool out, int nch) {
+    if constexpr (kFmt != (int)MP3G_OUT_S16) {
+      // float samples straight from the window's layout (replayed granules:
+      // zeros to no records, the same number of stores)
+      float pf[18];
+      if (out) {
+        f2 acc2[9];
+        window_acc(acc2);
+        pack_pcm(acc2, nch, pf);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 18; i++) pf[i] = 0.0f;
+      }
+      store_pcm_f32<kFmt>(pcm, geom, g, out, pf, lane_fresh() >> 5, lane_fresh() & 31);
+      return;
+    }
     if (out) {
-      float dw[16];
-      {
-        const float4* d4 = reinterpret_cast<const float4*>(&sh.dwin[k][0]);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const float4 v = d4[q];
-          dw[4 * q] = v.x;
-          dw[4 * q + 1] = v.y;
-          dw[4 * q + 2] = v.z;
-          dw[4 * q + 3] = v.w;
-        }
-      }
-      // accumulator pair p = output slots (2p, 2p+1).  Tap 2t of the pair reads
-      // column a of rows (v, v+1) and tap 2t+1 column b of rows (v-1, v),
-      // v = 2p - 2t: every operand pair is two rows of one column, i.e. one
-      // ds_read2_b32 that lands as the packed operand, and each feeds up to 8
-      // accumulator pairs.
-      const f2* RA = reinterpret_cast<const f2*>(&s.ring[ch][pa][0]);
-      const float* RB = &s.ring[ch][pb][0];
       f2 acc2[9];
-#pragma unroll
-      for (int p = 0; p < 9; p++) acc2[p] = bcast(0.0f);
-#pragma unroll
-      for (int v = -14; v <= 16; v += 2) {
-        const f2 A = RA[(kHist + v) / 2];  // slots (16+v, 17+v): 8-B aligned
-        const f2 B = {RB[kHist + v - 1], RB[kHist + v]};
-#pragma unroll
-        for (int t = 0; t < 8; t++) {
-          const int p = v / 2 + t;
-          if (p >= 0 && p < 9) {
-            acc2[p] = pfma(bcast(dw[2 * t]), A, acc2[p]);
-            acc2[p] = pfma(bcast(dw[2 * t + 1]), B, acc2[p]);
-          }
-        }
-      }
+      window_acc(acc2);
       // (L, R) sample pairs without LDS staging: one v_permlane32_swap per slot
       // pair hands lane i slot 2p's (L, R) and lane 32 + i slot 2p + 1's, so
       // every lane stores one dword per slot pair and the wave 2 x 128
@@ -1906,7 +2008,10 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
         // from it or from zero, as for any chunk); the exported state when
         // the piece ends the chunk (it then overwrites this pass's export)
         z.flags = (cd.flags & kChunkStateIn) | (pe == end ? (cd.flags & kChunkStateOut) : 0u);
-        z.reserved = 0;
+        // planar output: the piece writes into its stream's planes (the zone
+        // launch runs in this launch's format, and the other formats do not
+        // read the field: their code stays as it was)
+        z.stream_n = kFmt == (int)MP3G_OUT_F32_PLANAR ? cd.stream_n : 0u;
         zone_list[base + l] = z;
       }
       base += np;

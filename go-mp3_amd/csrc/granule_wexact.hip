@@ -217,6 +217,7 @@ __device__ __forceinline__ void init_state_exact(XWaveSmem& s, const mp3g_state*
 
 }  // namespace
 
+template <int kFmt>
 __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_granule* __restrict__ gran,
                                              const int16_t* __restrict__ coef, const mp3g_state* __restrict__ state_in,
                                              mp3g_state* __restrict__ state_out, int16_t* __restrict__ pcm,
@@ -231,7 +232,9 @@ __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_gra
 // every workgroup has read its length.  An
 // empty list ends every workgroup at once and leaves the counters alone, so
 // the launch pair needs no host-side state (graph replays included).
-template <bool kZones = false>
+// kFmt: the output format (MP3G_OUT_*) of the window's store stage, as in the
+// fast kernel; the arithmetic before it is the same in every format.
+template <bool kZones = false, int kFmt = (int)MP3G_OUT_S16>
 __global__ void __launch_bounds__(kLanes * kXWaves, 4)
 granule_wexact_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, const mp3g_granule* __restrict__ gran,
                       const int16_t* __restrict__ coef, const mp3g_state* __restrict__ state_in,
@@ -268,7 +271,7 @@ granule_wexact_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, c
       for (uint32_t ci = __builtin_amdgcn_readfirstlane(blockIdx.x * kXWaves + (threadIdx.x >> 6)); ci < live;
            ci += gridDim.x * kXWaves) {
         const ChunkDesc cd = chunks[ci];
-        wexact_chunk(cd, gran, coef, state_in, state_out, pcm, s, sh);
+        wexact_chunk<kFmt>(cd, gran, coef, state_in, state_out, pcm, s, sh);
       }
     }
     __syncthreads();  // the workgroup is done with the list
@@ -283,11 +286,12 @@ granule_wexact_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, c
     const uint32_t ci = __builtin_amdgcn_readfirstlane(blockIdx.x * kXWaves + (threadIdx.x >> 6));
     if (ci >= live) return;
     const ChunkDesc cd = chunks[ci];
-    wexact_chunk(cd, gran, coef, state_in, state_out, pcm, s, sh);
+    wexact_chunk<kFmt>(cd, gran, coef, state_in, state_out, pcm, s, sh);
   }
 }
 
 // One chunk in the reference's order (one wave).
+template <int kFmt>
 __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_granule* __restrict__ gran,
                                              const int16_t* __restrict__ coef, const mp3g_state* __restrict__ state_in,
                                              mp3g_state* __restrict__ state_out, int16_t* __restrict__ pcm,
@@ -304,6 +308,11 @@ __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_gra
   const mp3g_state* sin = state_in ? state_in + cd.stream : nullptr;
   f2 stp[9];
   init_state_exact(s, sin, init_in, lane, stp);
+  // (planar float output only: the stream's place, wave-uniform)
+  StreamGeom geom = {0u, 0u};
+  if constexpr (kFmt == (int)MP3G_OUT_F32_PLANAR)
+    geom = StreamGeom{(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)cd.stream_first),
+                      (uint32_t)__builtin_amdgcn_readfirstlane(cd.stream_n)};
 
   uint32_t cw[9] = {};
   if (w < end) {
@@ -387,8 +396,10 @@ __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_gra
       reinterpret_cast<uint4*>(&s.descn)[lane] = pd;
     }
 
-    // ---- window -> s16 PCM (frame.go:649-678) ----
-    uint32_t pk[9] = {};  // (replayed granules: stored to no records)
+    // ---- window -> PCM (frame.go:649-678) ----
+    // s16: one (L, R) dword per slot pair; float: the lane's 18 samples as
+    // they are (replayed granules: zeros stored to no records)
+    typename std::conditional<kFmt == (int)MP3G_OUT_S16, uint32_t[9], float[18]>::type pk = {};
     if (out) {
       // ring columns of output i = k's operands: V_j[i] (j even; V[16] has a
       // column of its own) and V_j[32 + i] (j odd); lane values recomputed
@@ -432,7 +443,8 @@ __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_gra
       for (int p = 0; p < 9; p++) acc2[p] = (f2){acc[2 * p] * 32767.0f, acc[2 * p + 1] * 32767.0f};
       pack_pcm(acc2, P.nch, pk);
     }
-    store_pcm(pcm, g, out, pk, lane_fresh() >> 5, lane_fresh() & 31);
+    if constexpr (kFmt == (int)MP3G_OUT_S16) store_pcm(pcm, g, out, pk, lane_fresh() >> 5, lane_fresh() & 31);
+    else store_pcm_f32<kFmt>(pcm, geom, g, out, pk, lane_fresh() >> 5, lane_fresh() & 31);
     wave_sync();
     // ---- history shift of the channels this granule touched: slots 18..33
     //      -> 0..15 of the 33 columns (lane (c, k): column k; k = 0 also V[16]) ----

@@ -14,14 +14,16 @@ constexpr uint32_t kChunkStateIn = 1u;   // stream starts from state_in[stream]
 constexpr uint32_t kChunkStateOut = 2u;  // this chunk ends its stream and exports state
 
 // One workgroup's work: decode granules [out_first, out_first + n_out) of the
-// stream that starts at stream_first (32 bytes).
+// stream that starts at stream_first and holds stream_n granules (32 bytes).
+// stream_n places the planes of MP3G_OUT_F32_PLANAR output; the other formats
+// do not read it.
 struct ChunkDesc {
   uint64_t out_first;
   uint64_t stream_first;
   uint32_t n_out;
   uint32_t stream;
   uint32_t flags;
-  uint32_t reserved;
+  uint32_t stream_n;
 };
 static_assert(sizeof(ChunkDesc) == 32, "ChunkDesc layout");
 
@@ -75,11 +77,14 @@ inline size_t zone_scratch_bytes(uint32_t cap) { return 32 + (size_t)cap * sizeo
 hipError_t zone_scratch_init(void* p, uint32_t cap);
 // zones: the fast kernel's deferred hot zones (required in fast mode, with
 // room for kZoneListPerChunk per chunk: hipErrorInvalidValue otherwise); hot_stats: run the counting build, which adds
-// its hot-granule work to the scratch's counters (the other kernels ignore both)
+// its hot-granule work to the scratch's counters (the other kernels ignore both).
+// out_format: MP3G_OUT_* -- d_out holds int16 or float32 samples accordingly;
+// the one-wave kernels (fast v3, exact v4) have an instantiation per format,
+// v2 writes s16 only (hipErrorInvalidValue otherwise).
 hipError_t launch_granule(int variant, const ChunkDesc* d_chunks, uint32_t n_chunks,
                           const mp3g_granule* d_gran, const int16_t* d_coef,
-                          const mp3g_state* d_state_in, mp3g_state* d_state_out, int16_t* d_pcm,
-                          const ZoneScratch* zones, bool hot_stats, hipStream_t stream);
+                          const mp3g_state* d_state_in, mp3g_state* d_state_out, void* d_out,
+                          uint32_t out_format, const ZoneScratch* zones, bool hot_stats, hipStream_t stream);
 // The fast kernel's hot-granule counters (granule_fast.hip, MP3G_FLAG_HOT_STATS):
 // [0] granules whose PCM the reference-order pass rewrites, [1] hot zones,
 // [2] hot granules the fast pass flagged, [3] granules re-run inside a wave
@@ -128,14 +133,14 @@ hipError_t upload_fast_tables(const FastTables& fast, const float* req);
 hipError_t fast_kernel_attributes(hipFuncAttributes* a, int* waves_per_block);
 hipError_t launch_fast(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
                        const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
-                       int16_t* d_pcm, unsigned long long* d_stamps, const ZoneScratch* zones, bool hot_stats,
-                       hipStream_t stream);
+                       void* d_out, uint32_t out_format, unsigned long long* d_stamps, const ZoneScratch* zones,
+                       bool hot_stats, hipStream_t stream);
 
 // Exact mode v4 (granule_wexact.hip, same TU as the fast kernel).
 hipError_t wexact_kernel_attributes(hipFuncAttributes* a, int* waves_per_block);
 hipError_t launch_wexact(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
                          const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
-                         int16_t* d_pcm, hipStream_t stream);
+                         void* d_out, uint32_t out_format, hipStream_t stream);
 
 // Standalone polyphase synthesis (granule_synth.hip, same TU): float32
 // frequency-inverted lines [n][2][576] -> s16 PCM, over a fast-mode plan.

@@ -129,16 +129,17 @@ int chunks_per_cu(int variant) {
 
 hipError_t launch_granule(int variant, const ChunkDesc* d_chunks, uint32_t n_chunks,
                           const mp3g_granule* d_gran, const int16_t* d_coef,
-                          const mp3g_state* d_state_in, mp3g_state* d_state_out, int16_t* d_pcm,
-                          const ZoneScratch* zones, bool hot_stats, hipStream_t stream) {
+                          const mp3g_state* d_state_in, mp3g_state* d_state_out, void* d_out,
+                          uint32_t out_format, const ZoneScratch* zones, bool hot_stats, hipStream_t stream) {
   if (n_chunks == 0) return hipSuccess;
   if (variant == kVariantFast)
-    return launch_fast(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, nullptr, zones, hot_stats,
-                       stream);
+    return launch_fast(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_out, out_format, nullptr, zones,
+                       hot_stats, stream);
   if (variant == kVariantExact4)
-    return launch_wexact(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, stream);
+    return launch_wexact(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_out, out_format, stream);
+  if (out_format != MP3G_OUT_S16) return hipErrorInvalidValue;  // (v2 has no float output)
   hipLaunchKernelGGL(v2::granule_fused_kernel, dim3(n_chunks), dim3(256), 0, stream, d_chunks,
-                     d_gran, d_coef, d_state_in, d_state_out, d_pcm);
+                     d_gran, d_coef, d_state_in, d_state_out, static_cast<int16_t*>(d_out));
   return hipGetLastError();
 }
 

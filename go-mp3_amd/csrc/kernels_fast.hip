@@ -58,33 +58,30 @@ hipError_t zone_scratch_init(void* p, uint32_t cap) {
   return hipMemcpy(p, h, sizeof(h), hipMemcpyHostToDevice);
 }
 
-hipError_t launch_fast(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
-                       const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
-                       int16_t* d_pcm, unsigned long long* d_stamps, const ZoneScratch* zones, bool hot_stats,
-                       hipStream_t stream) {
-  if (n_chunks == 0) return hipSuccess;
+namespace {
+
+// The fast launch pair of one output format: the fast kernel (with or
+// without the hot counters), then the zone launch in the same format.
+template <int kFmt>
+hipError_t launch_fast_fmt(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
+                           const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
+                           int16_t* d_pcm, const ZoneScratch* zones, bool hot_stats, hipStream_t stream) {
   const dim3 grid((n_chunks + v3::kWaves - 1) / v3::kWaves), block(64 * v3::kWaves);
-  // the production builds defer every hot zone to the plan's zone list: a
-  // fast launch without one is the diagnostic (stamped) build only
-  if (!d_stamps && (!zones || !zones->aux || zones->cap < (uint64_t)kZoneListPerChunk * n_chunks)) return hipErrorInvalidValue;
-  uint32_t* aux = zones ? zones->aux : nullptr;
-  if (d_stamps)  // (diagnostic: zones in the wave, no list)
-    hipLaunchKernelGGL(v3::granule_fast_kernel<true>, grid, block, 0, stream, d_chunks, n_chunks, d_gran, d_coef,
-                       d_state_in, d_state_out, d_pcm, static_cast<void*>(d_stamps));
-  else if (hot_stats && aux)
-    hipLaunchKernelGGL((v3::granule_fast_kernel<false, true>), grid, block, 0, stream, d_chunks, n_chunks, d_gran,
+  uint32_t* aux = zones->aux;
+  if (hot_stats)
+    hipLaunchKernelGGL((v3::granule_fast_kernel<false, true, kFmt>), grid, block, 0, stream, d_chunks, n_chunks, d_gran,
                        d_coef, d_state_in, d_state_out, d_pcm, static_cast<void*>(aux));
   else
-    hipLaunchKernelGGL(v3::granule_fast_kernel<false>, grid, block, 0, stream, d_chunks, n_chunks, d_gran, d_coef,
-                       d_state_in, d_state_out, d_pcm, static_cast<void*>(aux));
+    hipLaunchKernelGGL((v3::granule_fast_kernel<false, false, kFmt>), grid, block, 0, stream, d_chunks, n_chunks,
+                       d_gran, d_coef, d_state_in, d_state_out, d_pcm, static_cast<void*>(aux));
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess || !zones || d_stamps) return e;
+  if (e != hipSuccess) return e;
   // the zone launch: the exact v4 kernel over the list, its waves taking zone
   // after zone; one workgroup of 8 waves per MP3G_ZONE_CHUNKS_PER_WG chunks of
   // the launch, at most two per CU (an empty list ends every workgroup at
   // once: the fewer, the cheaper -- c2's 4,096 chunks get 128)
   const uint32_t blocks = std::max(16u, std::min<uint32_t>(n_chunks / MP3G_ZONE_CHUNKS_PER_WG, 512u));
-  hipLaunchKernelGGL(v4::granule_wexact_kernel<true>, dim3(blocks), dim3(64 * v4::kXWaves), 0, stream,
+  hipLaunchKernelGGL((v4::granule_wexact_kernel<true, kFmt>), dim3(blocks), dim3(64 * v4::kXWaves), 0, stream,
                      reinterpret_cast<const ChunkDesc*>(aux + 8), zones->cap, d_gran, d_coef, d_state_in,
                      d_state_out, d_pcm, aux);
   e = hipGetLastError();
@@ -96,6 +93,50 @@ hipError_t launch_fast(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_
   return e;
 }
 
+template <int kFmt>
+hipError_t launch_wexact_fmt(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
+                             const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
+                             int16_t* d_pcm, hipStream_t stream) {
+  const dim3 grid((n_chunks + v4::kXWaves - 1) / v4::kXWaves), block(64 * v4::kXWaves);
+  hipLaunchKernelGGL((v4::granule_wexact_kernel<false, kFmt>), grid, block, 0, stream, d_chunks, n_chunks, d_gran,
+                     d_coef, d_state_in, d_state_out, d_pcm, nullptr);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+// (the kernels take the output as int16_t* whatever the format: the float
+// instantiations cast it where they build their store resources)
+hipError_t launch_fast(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
+                       const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
+                       void* d_out, uint32_t out_format, unsigned long long* d_stamps, const ZoneScratch* zones,
+                       bool hot_stats, hipStream_t stream) {
+  if (n_chunks == 0) return hipSuccess;
+  int16_t* const d_pcm = static_cast<int16_t*>(d_out);
+  if (d_stamps) {  // (diagnostic: zones in the wave, no list; s16 only)
+    if (out_format != MP3G_OUT_S16) return hipErrorInvalidValue;
+    const dim3 grid((n_chunks + v3::kWaves - 1) / v3::kWaves), block(64 * v3::kWaves);
+    hipLaunchKernelGGL(v3::granule_fast_kernel<true>, grid, block, 0, stream, d_chunks, n_chunks, d_gran, d_coef,
+                       d_state_in, d_state_out, d_pcm, static_cast<void*>(d_stamps));
+    return hipGetLastError();
+  }
+  // the production builds defer every hot zone to the plan's zone list: a
+  // fast launch without one is the diagnostic (stamped) build only
+  if (!zones || !zones->aux || zones->cap < (uint64_t)kZoneListPerChunk * n_chunks) return hipErrorInvalidValue;
+  switch (out_format) {
+    case MP3G_OUT_S16:
+      return launch_fast_fmt<MP3G_OUT_S16>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, zones,
+                                           hot_stats, stream);
+    case MP3G_OUT_F32:
+      return launch_fast_fmt<MP3G_OUT_F32>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, zones,
+                                           hot_stats, stream);
+    case MP3G_OUT_F32_PLANAR:
+      return launch_fast_fmt<MP3G_OUT_F32_PLANAR>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
+                                                  zones, hot_stats, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
 hipError_t wexact_kernel_attributes(hipFuncAttributes* a, int* waves_per_block) {
   *waves_per_block = v4::kXWaves;
   return hipFuncGetAttributes(a, reinterpret_cast<const void*>(&v4::granule_wexact_kernel<false>));
@@ -103,12 +144,19 @@ hipError_t wexact_kernel_attributes(hipFuncAttributes* a, int* waves_per_block) 
 
 hipError_t launch_wexact(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
                          const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
-                         int16_t* d_pcm, hipStream_t stream) {
+                         void* d_out, uint32_t out_format, hipStream_t stream) {
   if (n_chunks == 0) return hipSuccess;
-  const dim3 grid((n_chunks + v4::kXWaves - 1) / v4::kXWaves), block(64 * v4::kXWaves);
-  hipLaunchKernelGGL(v4::granule_wexact_kernel<false>, grid, block, 0, stream, d_chunks, n_chunks, d_gran, d_coef,
-                     d_state_in, d_state_out, d_pcm, nullptr);
-  return hipGetLastError();
+  int16_t* const d_pcm = static_cast<int16_t*>(d_out);
+  switch (out_format) {
+    case MP3G_OUT_S16:
+      return launch_wexact_fmt<MP3G_OUT_S16>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, stream);
+    case MP3G_OUT_F32:
+      return launch_wexact_fmt<MP3G_OUT_F32>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, stream);
+    case MP3G_OUT_F32_PLANAR:
+      return launch_wexact_fmt<MP3G_OUT_F32_PLANAR>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
+                                                    stream);
+  }
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_synth(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran, const float* d_lines,
@@ -123,8 +171,8 @@ hipError_t launch_synth(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g
 hipError_t launch_fast_stamped(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
                                const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
                                int16_t* d_pcm, unsigned long long* d_stamps, hipStream_t stream) {
-  return launch_fast(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, d_stamps, nullptr, false,
-                     stream);
+  return launch_fast(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, MP3G_OUT_S16, d_stamps,
+                     nullptr, false, stream);
 }
 
 }  // namespace mp3g

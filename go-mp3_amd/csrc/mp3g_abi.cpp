@@ -258,6 +258,7 @@ int mp3g::plan_chunks(int device, const mp3g_stream* streams, uint32_t n_streams
       c.stream_first = S.first_granule;
       c.n_out = (uint32_t)(next - off);
       c.stream = s;
+      c.stream_n = S.n_granules;
       c.flags = (S.flags & MP3G_STREAM_STATE_IN) ? kChunkStateIn : 0u;
       if ((S.flags & MP3G_STREAM_STATE_OUT) && off + c.n_out == S.n_granules) c.flags |= kChunkStateOut;
       chunks->push_back(c);
@@ -284,8 +285,15 @@ int mp3g::plan_chunks(int device, const mp3g_stream* streams, uint32_t n_streams
 int mp3g::plan_launch(uint32_t mode, const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
                       const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out, int16_t* d_pcm,
                       const ZoneScratch* zones, hipStream_t stream) {
-  HIP_TRY(launch_granule(plan_variant(mode), d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
-                         zones, (mode & MP3G_FLAG_HOT_STATS) != 0, stream));
+  return plan_launch_out(mode, d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, MP3G_OUT_S16, zones,
+                         stream);
+}
+
+int mp3g::plan_launch_out(uint32_t mode, const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
+                          const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out, void* d_out,
+                          uint32_t out_format, const ZoneScratch* zones, hipStream_t stream) {
+  HIP_TRY(launch_granule(plan_variant(mode), d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_out,
+                         out_format, zones, (mode & MP3G_FLAG_HOT_STATS) != 0, stream));
   return MP3G_OK;
 }
 
@@ -444,10 +452,34 @@ int mp3g_plan_info(const mp3g_plan* p, uint64_t* n_chunks, uint64_t* n_granules,
   return MP3G_OK;
 }
 
+size_t mp3g_out_bytes_per_granule(uint32_t out_format) {
+  switch (out_format) {
+    case MP3G_OUT_S16: return MP3G_PCM_BYTES_PER_GRANULE;
+    case MP3G_OUT_F32:
+    case MP3G_OUT_F32_PLANAR: return 2 * MP3G_PCM_BYTES_PER_GRANULE;
+  }
+  return 0;
+}
+
 int mp3g_plan_execute(mp3g_plan* p, const mp3g_granule* d_gran, const int16_t* d_coef,
                       const mp3g_state* d_state_in, mp3g_state* d_state_out, int16_t* d_pcm,
                       void* hip_stream) {
+  return mp3g_plan_execute_out(p, d_gran, d_coef, d_state_in, d_state_out, d_pcm, MP3G_OUT_S16, hip_stream);
+}
+
+int mp3g_plan_execute_out(mp3g_plan* p, const mp3g_granule* d_gran, const int16_t* d_coef,
+                          const mp3g_state* d_state_in, mp3g_state* d_state_out, void* d_pcm,
+                          uint32_t out_format, void* hip_stream) {
+  if (!mp3g_out_bytes_per_granule(out_format)) return fail(MP3G_ERR_INVALID_ARGUMENT, "unknown output format");
   if (!p) return fail(MP3G_ERR_INVALID_ARGUMENT, "null plan");
+  if (out_format != MP3G_OUT_S16 && plan_variant(p->mode) == kVariantV2)
+    return fail(MP3G_ERR_UNSUPPORTED, "float output needs the one-wave kernels (no MP3G_FLAG_KERNEL_V2)");
+  if (out_format == MP3G_OUT_F32_PLANAR) {
+    // a plane pair is addressed with 31-bit byte offsets (granule_fast.hip store_pcm_f32)
+    for (const ChunkDesc& c : p->chunks)
+      if (c.stream_n >= MP3G_PLANAR_MAX_GRANULES)
+        return fail(MP3G_ERR_UNSUPPORTED, "planar output: stream of MP3G_PLANAR_MAX_GRANULES granules or more");
+  }
   if (p->chunks.empty()) return MP3G_OK;
   if (!d_gran || !d_coef || !d_pcm) return fail(MP3G_ERR_INVALID_ARGUMENT, "null device buffer");
   DeviceGuard guard(p->device);
@@ -456,8 +488,8 @@ int mp3g_plan_execute(mp3g_plan* p, const mp3g_granule* d_gran, const int16_t* d
     if ((c.flags & kChunkStateOut) && !d_state_out) return fail(MP3G_ERR_INVALID_ARGUMENT, "state_out needed");
   }
   const ZoneScratch zs{static_cast<uint32_t*>(p->d_zones), p->zone_cap};
-  return plan_launch(p->mode, p->d_chunks, (uint32_t)p->chunks.size(), d_gran, d_coef, d_state_in, d_state_out,
-                     d_pcm, p->d_zones ? &zs : nullptr, static_cast<hipStream_t>(hip_stream));
+  return plan_launch_out(p->mode, p->d_chunks, (uint32_t)p->chunks.size(), d_gran, d_coef, d_state_in, d_state_out,
+                         d_pcm, out_format, p->d_zones ? &zs : nullptr, static_cast<hipStream_t>(hip_stream));
 }
 
 // The fast kernel's hot-granule counters of this plan (MP3G_FLAG_HOT_STATS),
@@ -611,6 +643,16 @@ int mp3g_decode_host(int device, const mp3g_granule* granules, const int16_t* co
                      uint64_t n_granules, const mp3g_stream* streams, uint32_t n_streams,
                      const mp3g_state* state_in, mp3g_state* state_out, int16_t* pcm,
                      uint32_t mode) {
+  return mp3g_decode_host_out(device, granules, coeffs, n_granules, streams, n_streams, state_in, state_out, pcm,
+                              MP3G_OUT_S16, mode);
+}
+
+int mp3g_decode_host_out(int device, const mp3g_granule* granules, const int16_t* coeffs,
+                         uint64_t n_granules, const mp3g_stream* streams, uint32_t n_streams,
+                         const mp3g_state* state_in, mp3g_state* state_out, void* pcm,
+                         uint32_t out_format, uint32_t mode) {
+  const size_t out_bpg = mp3g_out_bytes_per_granule(out_format);
+  if (!out_bpg) return fail(MP3G_ERR_INVALID_ARGUMENT, "unknown output format");
   if (n_granules && (!granules || !coeffs || !pcm)) return fail(MP3G_ERR_INVALID_ARGUMENT, "null buffer");
   bool need_in = false, need_out = false;
   for (uint32_t s = 0; s < n_streams; s++) {
@@ -638,7 +680,7 @@ int mp3g_decode_host(int device, const mp3g_granule* granules, const int16_t* co
     mp3g_plan_destroy(plan);
   };
   const size_t gb = n_granules * sizeof(mp3g_granule), cb = n_granules * MP3G_COEF_PER_GRANULE * 2,
-               pb = n_granules * MP3G_PCM_BYTES_PER_GRANULE, sb = n_streams * sizeof(mp3g_state);
+               pb = n_granules * out_bpg, sb = n_streams * sizeof(mp3g_state);
   hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
   if (e == hipSuccess && gb) e = hipMalloc(&dg, gb);
   if (e == hipSuccess && cb) e = hipMalloc(&dc, cb);
@@ -658,8 +700,8 @@ int mp3g_decode_host(int device, const mp3g_granule* granules, const int16_t* co
     cleanup();
     return fail(MP3G_ERR_DEVICE, "hipMemcpyAsync(H2D)", e);
   }
-  st = mp3g_plan_execute(plan, (const mp3g_granule*)dg, (const int16_t*)dc, (const mp3g_state*)dsi,
-                         (mp3g_state*)dso, (int16_t*)dp, stream);
+  st = mp3g_plan_execute_out(plan, (const mp3g_granule*)dg, (const int16_t*)dc, (const mp3g_state*)dsi,
+                             (mp3g_state*)dso, dp, out_format, stream);
   if (st) {
     cleanup();
     return st;

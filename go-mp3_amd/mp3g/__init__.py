@@ -44,6 +44,10 @@ FLAG_KERNEL_V2 = 0x800  # exact mode via the workgroup v2 kernel (cross-check of
 FLAG_HOT_STATS = 0x1000  # fast plans: count the hot-granule fallback's work (Plan.hot_stats)
 STATE_IN, STATE_OUT = 1, 2
 MP3G_PCM_BYTES_PER_GRANULE = 2304  # include/mp3g.h: 576 stereo s16 samples
+# output formats (include/mp3g.h MP3G_OUT_*): s16 [n, 576, 2]; float32 in the
+# same order; float32 planar -- stream (first F, n granules) owns floats
+# [F * 1152, (F + n) * 1152), plane ch at F * 1152 + ch * n * 576
+OUT_S16, OUT_F32, OUT_F32_PLANAR = 0, 1, 2
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "invalid granule", 3: "no device", 4: "device error",
           5: "out of memory", 6: "parse error", 7: "eof", 8: "unsupported", 9: "no Xing/Info header",
@@ -96,6 +100,11 @@ def lib():
         if hasattr(L, "mp3g_plan_hot_stats"):  # ABI 5 (an older build through MP3G_LIB: A/B runs)
             L.mp3g_plan_hot_stats.argtypes = [vp, C.POINTER(u64), C.c_int]
         L.mp3g_decode_host.argtypes = [C.c_int, vp, vp, u64, vp, u32, vp, vp, vp, u32]
+        if hasattr(L, "mp3g_plan_execute_out"):  # (an older build through MP3G_LIB: A/B runs)
+            L.mp3g_out_bytes_per_granule.argtypes = [u32]
+            L.mp3g_out_bytes_per_granule.restype = C.c_size_t
+            L.mp3g_plan_execute_out.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp]
+            L.mp3g_decode_host_out.argtypes = [C.c_int, vp, vp, u64, vp, u32, vp, vp, vp, u32, u32]
         L.mp3g_plan_debug_phases.argtypes = [vp, vp, vp, vp, C.POINTER(u64), vp]
         L.mp3g_plan_debug_timeline.argtypes = [vp, vp, vp, vp, C.POINTER(u64), vp]
         if hasattr(L, "mp3g_debug_clock_probe"):  # (an older build through MP3G_LIB: A/B runs)
@@ -178,12 +187,32 @@ def validate(granules, coeffs):
     return st, bad.value
 
 
+def out_bytes_per_granule(out_format):
+    """Output bytes per granule of OUT_* (2304 / 4608 / 4608); 0 for an unknown format."""
+    return int(lib().mp3g_out_bytes_per_granule(int(out_format)))
+
+
+def planar_views(out, streams):
+    """The [2, n * 576] view of each stream in an OUT_F32_PLANAR buffer (a flat
+    numpy array or torch tensor of float32, 1152 per granule slot): plane ch
+    of stream (F, n) starts at float F * 1152 + ch * n * 576."""
+    views = []
+    for s in np.asarray(streams, dtype=STREAM_DTYPE):
+        f, n = int(s["first_granule"]), int(s["n_granules"])
+        views.append(out[f * 1152:(f + n) * 1152].reshape(2, n * 576))
+    return views
+
+
 def decode_host(granules, coeffs, streams=None, state_in=None, state_out=None, mode=MODE_EXACT,
-                device=0):
-    """Synchronous decode of host arrays (the cgo drop-in entry, mp3g_decode_host).
+                device=0, out_format=OUT_S16):
+    """Synchronous decode of host arrays (the cgo drop-in entry, mp3g_decode_host /
+    mp3g_decode_host_out).
 
     granules: GRANULE_DTYPE[n]; coeffs: int16[n, 2, 576]; streams: STREAM_DTYPE[s]
-    (default: one stream covering everything).  Returns (pcm int16[n, 576, 2], state_out).
+    (default: one stream covering everything).  Returns (pcm, state_out): pcm is
+    int16[n, 576, 2] (OUT_S16), float32[n, 576, 2] (OUT_F32) or a flat float32
+    array of n * 1152 (OUT_F32_PLANAR: planar_views(pcm, streams) gives each
+    stream's [2, n * 576]).  trunc(float * 32768) is the s16 sample.
     """
     granules = np.ascontiguousarray(granules, dtype=GRANULE_DTYPE)
     coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
@@ -196,9 +225,14 @@ def decode_host(granules, coeffs, streams=None, state_in=None, state_out=None, m
         state_in = np.ascontiguousarray(state_in, dtype=STATE_DTYPE)
     if state_out is None:
         state_out = np.zeros(len(streams), STATE_DTYPE)
-    pcm = np.zeros((n, 576, 2), np.int16)
-    _check(lib().mp3g_decode_host(device, _ptr(granules), _ptr(coeffs), n, _ptr(streams),
-                                  len(streams), _ptr(state_in), _ptr(state_out), _ptr(pcm), mode))
+    if out_format == OUT_S16:
+        pcm = np.zeros((n, 576, 2), np.int16)
+        _check(lib().mp3g_decode_host(device, _ptr(granules), _ptr(coeffs), n, _ptr(streams),
+                                      len(streams), _ptr(state_in), _ptr(state_out), _ptr(pcm), mode))
+        return pcm, state_out
+    pcm = np.zeros(n * 1152 if out_format == OUT_F32_PLANAR else (n, 576, 2), np.float32)
+    _check(lib().mp3g_decode_host_out(device, _ptr(granules), _ptr(coeffs), n, _ptr(streams), len(streams),
+                                      _ptr(state_in), _ptr(state_out), _ptr(pcm), int(out_format), mode))
     return pcm, state_out
 
 
@@ -413,6 +447,47 @@ def decode_streams(datas, mode=MODE_EXACT, n_threads=0, device=0):
     return _take(pcm, k, np.int16, (k, 576, 2)), streams, status[:len(datas)]
 
 
+def decode_streams_tensor(datas, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, n_threads=0, device=0):
+    """Bitstreams in, one device tensor out: the host scan, one upload, then the
+    main-data kernel and the plan kernel on torch-owned buffers and the
+    current torch stream -- no PCM comes back to the host.  Returns when the
+    kernels are done (the plan and the input buffers are released then).
+
+    Returns (out, views, streams, end_status).  out: a float32 (OUT_S16:
+    int16) tensor of 1152 samples per granule on cuda:device; views[k] is
+    stream k's part of it -- [2, T] for OUT_F32_PLANAR, [T, 2] for the
+    interleaved formats, T = 576 * n_granules.  streams / end_status as
+    decode_streams.  No gapless trimming: slice a view with LameInfo.trim."""
+    import torch
+    if not out_bytes_per_granule(out_format):
+        raise Mp3gError(1, "unknown output format")
+    s = scan_streams(datas, n_threads=n_threads)
+    streams, n = s["streams"], len(s["granules"])
+    dev = torch.device("cuda", device)
+    out = torch.empty(n * 1152, dtype=torch.int16 if out_format == OUT_S16 else torch.float32, device=dev)
+    if n:
+        d_g = torch.from_numpy(s["granules"].view(np.uint8)).to(dev)
+        d_j = torch.from_numpy(s["jobs"].view(np.uint8)).to(dev)
+        d_m = torch.from_numpy(s["main_data"]).to(dev)
+        d_c = torch.empty(n * 1152, dtype=torch.int16, device=dev)
+        plan = Plan(streams, mode=mode, device=device)
+        st = torch.cuda.current_stream(dev)
+        # (rows to count1: the one-wave plan kernels read no further)
+        flags = (0 if mode & FLAG_KERNEL_V2 else HUFF_ROWS_COUNT1) | huffman_stage_flags(s["jobs"], n)
+        huffman_execute(d_j, n, d_m, d_g, d_c, stream=st.cuda_stream, device=device, flags=flags)
+        plan.execute(d_g, d_c, out, stream=st.cuda_stream, out_format=out_format)
+        # the inputs and the plan's chunk table are read by the kernels: they
+        # are released once the stream is done with them
+        st.synchronize()
+        plan.close()
+    if out_format == OUT_F32_PLANAR:
+        views = planar_views(out, streams)
+    else:
+        views = [out[int(f) * 1152:(int(f) + int(k)) * 1152].reshape(int(k) * 576, 2)
+                 for f, k in zip(streams["first_granule"], streams["n_granules"])]
+    return out, views, streams, s["end_status"]
+
+
 def _host_buffer(out, want_int16):
     """(pointer, size in bytes) of a caller's writable, C-contiguous HOST
     buffer -- a numpy array or a CPU torch tensor (pinned or not).  The
@@ -604,15 +679,22 @@ class Plan:
         _check(lib().mp3g_plan_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"chunks": a.value, "granules": b.value, "halo_granules": c.value}
 
-    def execute(self, d_gran, d_coef, d_pcm, d_state_in=None, d_state_out=None, stream=None):
-        """Pointers are ints (device addresses) or torch tensors; stream: hipStream_t int."""
+    def execute(self, d_gran, d_coef, d_pcm, d_state_in=None, d_state_out=None, stream=None, out_format=OUT_S16):
+        """Pointers are ints (device addresses) or torch tensors; stream: hipStream_t int.
+        out_format: OUT_* -- d_pcm holds out_bytes_per_granule(out_format) bytes per
+        granule slot (mp3g_plan_execute_out)."""
         def p(x):
             if x is None:
                 return None
             return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        _check(lib().mp3g_plan_execute(self._h, p(d_gran), p(d_coef), p(d_state_in),
-                                       p(d_state_out), p(d_pcm),
-                                       C.c_void_p(stream) if stream else None))
+        if out_format == OUT_S16:
+            _check(lib().mp3g_plan_execute(self._h, p(d_gran), p(d_coef), p(d_state_in),
+                                           p(d_state_out), p(d_pcm),
+                                           C.c_void_p(stream) if stream else None))
+        else:
+            _check(lib().mp3g_plan_execute_out(self._h, p(d_gran), p(d_coef), p(d_state_in),
+                                               p(d_state_out), p(d_pcm), int(out_format),
+                                               C.c_void_p(stream) if stream else None))
 
     def synth_execute(self, d_gran, d_lines, d_pcm, d_state_in=None, d_state_out=None, stream=None):
         """Standalone polyphase synthesis (mp3g_plan_synth_execute, frame.go:630-688) on

@@ -45,7 +45,9 @@ extern "C" {
  * 5: mp3g_plan_hot_stats and MP3G_FLAG_HOT_STATS (the fast kernel's
  *    hot-granule fallback counters); a fast-mode plan owns a zone list its
  *    launches share, so executions of one plan must be stream-ordered.
- *    (Compatible additions since: the diagnostic mp3g_debug_clock_probe.) */
+ *    (Compatible additions since: the diagnostic mp3g_debug_clock_probe;
+ *    float32 PCM output -- MP3G_OUT_*, mp3g_out_bytes_per_granule,
+ *    mp3g_plan_execute_out and mp3g_decode_host_out.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -112,6 +114,25 @@ typedef struct mp3g_granule {
 /* PCM: int16 [n_granules][576][2] = the bytes Decode() returns, concatenated
  * (frame.go:134: granule gr at byte 2304*gr; mono duplicated, frame.go:671-678). */
 #define MP3G_PCM_BYTES_PER_GRANULE (MP3G_LINES * 2 * 2)
+
+/* ---- output formats (mp3g_plan_execute_out / mp3g_decode_host_out) -------
+ * The sample value is the same in every format and both modes.  With
+ * t = sum * 32767 as the window stage computes it (frame.go:649-662),
+ *   s16:   (int16)trunc(clamp(t, -32767, 32767))        (frame.go:663-669)
+ *   float: f = clamp(t, -32767, 32767) * 2^-15          (no truncation)
+ * so (int16)trunc(f * 32768) is exactly the s16 sample of the same plan and
+ * |f| <= 32767/32768.  Mono granules write channel 0 to both channels / planes
+ * (frame.go:671-678).  The exported state does not depend on the format.
+ * MP3G_OUT_F32_PLANAR needs streams that do not overlap, each of fewer than
+ * MP3G_PLANAR_MAX_GRANULES granules (MP3G_ERR_UNSUPPORTED otherwise). */
+#define MP3G_OUT_S16        0u /* int16 [n_granules][576][2]: the layout above             */
+#define MP3G_OUT_F32        1u /* float [n_granules][576][2]: same order, float32          */
+#define MP3G_OUT_F32_PLANAR 2u /* float; stream s (first F, n granules) owns floats
+                                  [F*1152, (F+n)*1152): plane ch at F*1152 + ch*n*576,
+                                  n*576 samples, in time order                             */
+#define MP3G_PLANAR_MAX_GRANULES 900000u /* (a plane pair is addressed with 31-bit byte offsets) */
+/* Output bytes per granule of a format: 2304 / 4608 / 4608; 0 = unknown format. */
+size_t mp3g_out_bytes_per_granule(uint32_t out_format);
 
 /* ---- cross-granule DSP state (reference Frame.store / Frame.vVec) ------- */
 /* Layout identical to the reference fields (frame.go:48-49): copying a
@@ -199,6 +220,18 @@ int mp3g_plan_info(const mp3g_plan* plan, uint64_t* n_chunks, uint64_t* n_granul
 int mp3g_plan_execute(mp3g_plan* plan, const mp3g_granule* d_granules,
                       const int16_t* d_coeffs, const mp3g_state* d_state_in,
                       mp3g_state* d_state_out, int16_t* d_pcm, void* hip_stream);
+/* The same with the output format chosen per call (MP3G_OUT_*): d_out holds
+ * mp3g_out_bytes_per_granule(out_format) bytes per granule slot.
+ * mp3g_plan_execute is the MP3G_OUT_S16 case.  An unknown format is
+ * MP3G_ERR_INVALID_ARGUMENT (checked before any device call); a float format
+ * on an MP3G_FLAG_KERNEL_V2 plan is MP3G_ERR_UNSUPPORTED (the one-wave kernels,
+ * fast v3 and exact v4, write floats straight from the window's registers;
+ * the cross-check kernel stays s16).  No reference counterpart: go-mp3's
+ * Decode returns s16 bytes only (frame.go:121-137). */
+int mp3g_plan_execute_out(mp3g_plan* plan, const mp3g_granule* d_granules,
+                          const int16_t* d_coeffs, const mp3g_state* d_state_in,
+                          mp3g_state* d_state_out, void* d_out, uint32_t out_format,
+                          void* hip_stream);
 
 /* Standalone polyphase synthesis: go-mp3's subbandSynthesis
  * (internal/frame/frame.go:630-688, called per channel at frame.go:133) over
@@ -236,6 +269,13 @@ int mp3g_decode_host(int device, const mp3g_granule* granules, const int16_t* co
                      uint64_t n_granules, const mp3g_stream* streams, uint32_t n_streams,
                      const mp3g_state* state_in, mp3g_state* state_out, int16_t* pcm,
                      uint32_t mode);
+/* The same with an output format (MP3G_OUT_*): `out` holds
+ * n_granules * mp3g_out_bytes_per_granule(out_format) bytes; mp3g_decode_host
+ * is the MP3G_OUT_S16 case. */
+int mp3g_decode_host_out(int device, const mp3g_granule* granules, const int16_t* coeffs,
+                         uint64_t n_granules, const mp3g_stream* streams, uint32_t n_streams,
+                         const mp3g_state* state_in, mp3g_state* state_out, void* out,
+                         uint32_t out_format, uint32_t mode);
 
 /* ---- host bitstream parse (CPU only) -----------------
  * The part of go-mp3's frame.Read that feeds Decode: tags (source.go:42-83),
