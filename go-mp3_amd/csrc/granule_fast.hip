@@ -153,8 +153,9 @@ struct __align__(16) SharedSmem {
   // ds_read_b64 reads both
   uint2 lbd[kCombos][32];
   __device__ uint32_t lband_at(int c, int k) const { return lbd[c][k].x; }
-  // FastTables::p43: sign(x) |x|^(4/3) of x = -128..127 at byte offset
-  // 4 x + 512 -- the long-block requantize is a table read and one multiply
+  // FastTables::p43: sign(x) |x|^(4/3) of x = -kFastP43 / 2 .. kFastP43 / 2 - 1
+  // at byte offset 4 x + 2 kFastP43 -- the long-block requantize is a table
+  // read and one multiply
   float p43[kFastP43];
 };
 // per-wave working set 9.1 KB.  The workgroup (8 waves + shared tables) must
@@ -318,6 +319,13 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+
+// s_waitcnt vmcnt(0) alone: every vector-memory operation of the wave done,
+// LDS / scalar / export counters left alone (gfx9 encoding: vmcnt in bits 3:0
+// and 15:14, expcnt 6:4 = 7 and lgkmcnt 11:8 = 15 are "no wait").  The builtin,
+// not an asm string: the compiler's wait-count pass then knows that nothing
+// issued before it is still pending.
+__device__ __forceinline__ void settle_vmem() { __builtin_amdgcn_s_waitcnt(0x0f70); }
 
 // Branch-free selects (v_bfi_b32 / v_cndmask): keeps the compiler from turning
 // a per-lane choice between two cheap values into exec-mask branches.
@@ -1273,6 +1281,17 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
   }
 #endif
   shared_init();
+  // The loads above (coefficients, dv, dvn, entry state) settled here, once per
+  // chunk.  Left in flight, they reach the granule loop's header as pending
+  // vector-memory operations, and the compiler's wait-count pass, merging that
+  // state with the back edge's, put static waits for them into the loop
+  // (s_waitcnt vmcnt(2) before the first read of dv, vmcnt(1) before the
+  // first use of cw): in the steady state those only park the wave until all
+  // but two (one) of the previous granule's nine PCM stores are acknowledged.
+  // After this wait the loop waits for vector memory at its back edge only
+  // (the prefetch, leaving the stores in flight) and on the rare paths that
+  // issue loads of their own.  tools/loop_boundary.sh reads it off the ISA.
+  settle_vmem();
   __syncthreads();  // the only workgroup barrier: the waves are independent from here on
 
   // PCM of a granule: one dword (L, R) per lane and slot pair
@@ -1533,9 +1552,10 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       for (int q = 0; q < 9; q++)  // band starts among lines 2..2q (bits 0..4q-1 of d4)
         gq[q] = *reinterpret_cast<const float*>(eb + __builtin_popcount(d4 & (q == 8 ? ~0u : (1u << (4 * q)) - 1u)));
       // x^(4/3) 2^(n4/4) (frame.go:187-200) as p43[x] times the band gain.
-      // Both lines of a dword at once: 4 x + 512 per 16-bit half (one
-      // v_pk_mad_u16) is the table's byte offset for x = -128..127 and >= 1024
-      // for every other |x| <= 8206 (mp3g_validate's bound); lanes holding such
+      // Both lines of a dword at once: 4 x + 2 kFastP43 per 16-bit half (one
+      // v_pk_mad_u16) is the table's byte offset for x = -kFastP43 / 2 ..
+      // kFastP43 / 2 - 1 and >= 4 kFastP43 (past the table) for every other
+      // |x| <= 8206 (mp3g_validate's bound); lanes holding such
       // a line (c3: ~0.2 % of lanes, 12 % of granules have one) redo their 18
       // lines arithmetically below, and their table reads stay inside the
       // workgroup's LDS (offsets < 64 KiB) and are discarded.
