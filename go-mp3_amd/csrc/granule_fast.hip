@@ -1017,6 +1017,106 @@ __device__ __forceinline__ void store_pcm_f32(int16_t* pcm, StreamGeom sg, uint3
   }
 }
 
+// ---- mono downmix output (MP3G_OUT_S16_MONO / MP3G_OUT_F32_MONO) ----
+// The s16 pack's v_permlane32_swap brings the two channels of a sample into
+// one lane: lane i holds slot 2p's (L, R), lane 32 + i slot 2p + 1's.  The
+// downmix is one add there, and every lane owns ONE sample per slot pair:
+// sample 64 p + lane of the granule's 576, so a store of the wave covers 64
+// consecutive samples.
+//   s16:   m = (L + R) >> 1 on the s16 samples (arithmetic shift: floor)
+//   float: m = (fL + fR) * 0.5f on the float samples (one rounded add; the
+//          halving is exact)
+// A mono granule gives channel 0's sample as it is (wave-uniform branch).
+constexpr bool fmt_is_mono(int fmt) { return fmt == (int)MP3G_OUT_S16_MONO || fmt == (int)MP3G_OUT_F32_MONO; }
+#ifndef MP3G_MONO_S16_PACK
+#define MP3G_MONO_S16_PACK 0  // (A/B) s16 mono: pair neighbouring lanes' samples (one DPP move), dword stores from the even lanes
+#endif
+__device__ __forceinline__ void pack_pcm_mono(const f2 acc2[9], int nch, uint32_t pm[9]) {
+  auto pack = [&](auto mono) {
+#pragma unroll
+    for (int p = 0; p < 9; p++) {
+      const int a = (int)__builtin_amdgcn_fmed3f(acc2[p].x, -32767.0f, 32767.0f);
+      const int b = (int)__builtin_amdgcn_fmed3f(acc2[p].y, -32767.0f, 32767.0f);
+      const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+      const int m = decltype(mono)::value ? (int)r[0] : ((int)r[0] + (int)r[1]) >> 1;
+#if MP3G_MONO_S16_PACK
+      // lane 2j takes lane 2j + 1's sample (quad_perm [1, 1, 3, 3]) into its high half
+      const int n = __builtin_amdgcn_update_dpp(0, m, 0xF5, 0xf, 0xf, false);
+      pm[p] = __builtin_amdgcn_perm((uint32_t)n, (uint32_t)m, 0x05040100u);
+#else
+      pm[p] = (uint32_t)m;
+#endif
+    }
+  };
+  if (nch == 2) pack(std::false_type{});
+  else pack(std::true_type{});
+}
+
+__device__ __forceinline__ void pack_pcm_mono(const f2 acc2[9], int nch, float pm[9]) {
+  auto pack = [&](auto mono) {
+#pragma unroll
+    for (int p = 0; p < 9; p++) {
+      const float a = __builtin_amdgcn_fmed3f(acc2[p].x, -32767.0f, 32767.0f) * (1.0f / 32768.0f);
+      const float b = __builtin_amdgcn_fmed3f(acc2[p].y, -32767.0f, 32767.0f) * (1.0f / 32768.0f);
+      const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b),
+                                                      false, false);
+      const float fl = __builtin_bit_cast(float, (uint32_t)r[0]), fr = __builtin_bit_cast(float, (uint32_t)r[1]);
+      pm[p] = decltype(mono)::value ? fl : (fl + fr) * 0.5f;
+    }
+  };
+  if (nch == 2) pack(std::false_type{});
+  else pack(std::true_type{});
+}
+
+// The registers a lane hands the store stage, per format: s16 (L, R) dwords,
+// the lane's 18 float samples, or one mono sample per slot pair.
+template <int kFmt>
+struct PcmRegs {
+  typedef float type[18];
+};
+template <>
+struct PcmRegs<(int)MP3G_OUT_S16> {
+  typedef uint32_t type[9];
+};
+template <>
+struct PcmRegs<(int)MP3G_OUT_S16_MONO> {
+  typedef uint32_t type[9];
+};
+template <>
+struct PcmRegs<(int)MP3G_OUT_F32_MONO> {
+  typedef float type[9];
+};
+
+// Mono samples of granule g: sample 64 p + lane, non-temporal and issued for
+// replayed granules too (no records), nine stores per lane like the s16 path.
+// The resource spans exactly the granule: 1,152 B (s16) or 2,304 B (float).
+//   s16:   16-bit stores, 128 contiguous bytes per store of the wave
+//          (MP3G_MONO_S16_PACK: dwords from the even lanes; the odd lanes'
+//          offset lies past the records)
+//   float: one dword per lane, 256 contiguous bytes
+__device__ __forceinline__ void store_pcm_mono(int16_t* pcm, uint32_t g, bool out, const uint32_t pm[9], int lane) {
+  const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
+      pcm + (size_t)g * MP3G_LINES, (short)0, out ? MP3G_PCM_BYTES_PER_GRANULE / 2 : 0, 0x00020000);
+#if MP3G_MONO_S16_PACK
+  const int off = (lane & 1) ? kNoRecord : 2 * lane;
+#pragma unroll
+  for (int p = 0; p < 9; p++) __builtin_amdgcn_raw_buffer_store_b32(pm[p], rp, off + 128 * p, 0, MP3G_PCM_STORE_AUX);
+#else
+#pragma unroll
+  for (int p = 0; p < 9; p++)
+    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)pm[p], rp, 2 * (64 * p + lane), 0, MP3G_PCM_STORE_AUX);
+#endif
+}
+
+__device__ __forceinline__ void store_pcm_mono(int16_t* pcm, uint32_t g, bool out, const float pm[9], int lane) {
+  const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
+      reinterpret_cast<float*>(pcm) + (size_t)g * MP3G_LINES, (short)0, out ? MP3G_PCM_BYTES_PER_GRANULE : 0, 0x00020000);
+#pragma unroll
+  for (int p = 0; p < 9; p++)
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pm[p]), rp, 4 * (64 * p + lane), 0,
+                                          MP3G_PCM_STORE_AUX);
+}
+
 // Entry state of a replay start: overlap store in registers, V history as X
 // vectors, from the stream's state_in (init_in) or zero.  stp[q] =
 // (store[q], store[17-q]), each element times the frequency-inversion sign of
@@ -1345,7 +1445,21 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     geom = StreamGeom{(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)cd.stream_first),
                       (uint32_t)__builtin_amdgcn_readfirstlane(cd.stream_n)};
   auto window_store = [&](uint32_t g, bool out, int nch) {
-    if constexpr (kFmt != (int)MP3G_OUT_S16) {
+    if constexpr (fmt_is_mono(kFmt)) {
+      // one downmixed sample per lane and slot pair (replayed granules: zeros
+      // to no records, the same number of stores)
+      typename PcmRegs<kFmt>::type pm;
+      if (out) {
+        f2 acc2[9];
+        window_acc(acc2);
+        pack_pcm_mono(acc2, nch, pm);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 9; i++) pm[i] = 0;
+      }
+      store_pcm_mono(pcm, g, out, pm, lane_fresh());
+      return;
+    } else if constexpr (kFmt != (int)MP3G_OUT_S16) {
       // float samples straight from the window's layout (replayed granules:
       // zeros to no records, the same number of stores)
       float pf[18];

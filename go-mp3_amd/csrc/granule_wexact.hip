@@ -398,8 +398,9 @@ __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_gra
 
     // ---- window -> PCM (frame.go:649-678) ----
     // s16: one (L, R) dword per slot pair; float: the lane's 18 samples as
-    // they are (replayed granules: zeros stored to no records)
-    typename std::conditional<kFmt == (int)MP3G_OUT_S16, uint32_t[9], float[18]>::type pk = {};
+    // they are; mono: one downmixed sample per slot pair (replayed granules:
+    // zeros stored to no records)
+    typename PcmRegs<kFmt>::type pk = {};
     if (out) {
       // ring columns of output i = k's operands: V_j[i] (j even; V[16] has a
       // column of its own) and V_j[32 + i] (j odd); lane values recomputed
@@ -441,9 +442,11 @@ __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_gra
       f2 acc2[9];
 #pragma unroll
       for (int p = 0; p < 9; p++) acc2[p] = (f2){acc[2 * p] * 32767.0f, acc[2 * p + 1] * 32767.0f};
-      pack_pcm(acc2, P.nch, pk);
+      if constexpr (fmt_is_mono(kFmt)) pack_pcm_mono(acc2, P.nch, pk);
+      else pack_pcm(acc2, P.nch, pk);
     }
-    if constexpr (kFmt == (int)MP3G_OUT_S16) store_pcm(pcm, g, out, pk, lane_fresh() >> 5, lane_fresh() & 31);
+    if constexpr (fmt_is_mono(kFmt)) store_pcm_mono(pcm, g, out, pk, lane_fresh());
+    else if constexpr (kFmt == (int)MP3G_OUT_S16) store_pcm(pcm, g, out, pk, lane_fresh() >> 5, lane_fresh() & 31);
     else store_pcm_f32<kFmt>(pcm, geom, g, out, pk, lane_fresh() >> 5, lane_fresh() & 31);
     wave_sync();
     // ---- history shift of the channels this granule touched: slots 18..33

@@ -775,6 +775,8 @@ bool md_resize(RawMd* r, size_t n) {
   r->n = n;
   return true;
 }
+void md_clear_overflow(std::vector<uint8_t>*) {}
+void md_clear_overflow(RawMd* r) { r->overflow = false; }
 }  // namespace
 
 St FrameScanner::next(Source& s, ScannedFrame* out, std::vector<uint8_t>* md) { return next_impl(s, out, md); }
@@ -813,8 +815,18 @@ St FrameScanner::next_impl(Source& s, ScannedFrame* out, Md* md) {
   const int offset = si.main_data_begin;
   const bool underflow = have_prev_ && offset > g0 - prev_start_;
   const int64_t vstart = !have_prev_ ? g0 : underflow ? prev_start_ : g0 - offset;
-  if (!md_resize(md, (size_t)(g0 + size))) return St::kErr;
   bool sr;
+  if (!md_resize(md, (size_t)(g0 + size))) {
+    // A sink sized by prescan() has no room for a frame whose main data the
+    // source ends in (the pre-pass does not count it): that frame ends the
+    // stream as a short read does below, and is no overflow.
+    uint8_t cut[1500];
+    if (s.read_full(cut, size, &sr) < size) {
+      md_clear_overflow(md);
+      return sr ? St::kEof : St::kErr;
+    }
+    return St::kErr;
+  }
   if (s.read_full(md->data() + g0, size, &sr) < size) {
     md_resize(md, (size_t)g0);
     return sr ? St::kEof : St::kErr;

@@ -504,6 +504,21 @@ int mp3g_decode_streams_into(int device, uint32_t n_streams, const uint8_t* cons
                              int n_threads, uint32_t mode, uint32_t n_groups, int16_t* pcm,
                              uint64_t pcm_cap_granules, uint64_t* n_granules, mp3g_stream* streams,
                              int* end_status) {
+  return mp3g_decode_streams_into_out(device, n_streams, datas, lens, n_threads, mode, n_groups, pcm, MP3G_OUT_S16,
+                                      pcm_cap_granules, n_granules, streams, end_status);
+}
+
+int mp3g_decode_streams_into_out(int device, uint32_t n_streams, const uint8_t* const* datas, const size_t* lens,
+                                 int n_threads, uint32_t mode, uint32_t n_groups, void* out, uint32_t out_format,
+                                 uint64_t out_cap_granules, uint64_t* n_granules, mp3g_stream* streams,
+                                 int* end_status) {
+  // bytes per granule slot of the output, the group buffers and the copies
+  const size_t bpg = mp3g_out_bytes_per_granule(out_format);
+  if (!bpg) return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "decode_streams_into: unknown output format");
+  if (out_format != MP3G_OUT_S16 && !mode_reads_to_count1(mode))
+    return abi_fail(MP3G_ERR_UNSUPPORTED,
+                    "decode_streams_into: this output format needs the one-wave kernels (no MP3G_FLAG_KERNEL_V2)");
+  uint8_t* const pcm = static_cast<uint8_t*>(out);
   if (!n_granules || (n_streams && (!datas || !lens || !streams || !end_status)))
     return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "null argument");
   *n_granules = 0;
@@ -519,7 +534,11 @@ int mp3g_decode_streams_into(int device, uint32_t n_streams, const uint8_t* cons
   }
   const uint64_t total = g_at[n_streams];
   *n_granules = total;
-  if (total > pcm_cap_granules) return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "pcm holds fewer blocks than needed");
+  if (total > out_cap_granules) return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "pcm holds fewer blocks than needed");
+  if (out_format == MP3G_OUT_F32_PLANAR)  // (a plane pair is addressed with 31-bit byte offsets)
+    for (uint32_t k = 0; k < n_streams; k++)
+      if (pg[k] >= MP3G_PLANAR_MAX_GRANULES)
+        return abi_fail(MP3G_ERR_UNSUPPORTED, "planar output: stream of MP3G_PLANAR_MAX_GRANULES granules or more");
   for (uint32_t k = 0; k < n_streams; k++) {
     streams[k].first_granule = g_at[k];
     streams[k].n_granules = 0;
@@ -603,8 +622,9 @@ int mp3g_decode_streams_into(int device, uint32_t n_streams, const uint8_t* cons
   }
   {
     // Three streams, so that a group's PCM copy-out (the long pole: 2,304 B
-    // per granule over PCIe) runs back to back with the next group's
-    // bitstream upload (the other direction) and kernels:
+    // per granule over PCIe in s16 stereo, `bpg` in general) runs back to
+    // back with the next group's bitstream upload (the other direction) and
+    // kernels:
     //   up:   [wait kern(g-2)] H2D granules, jobs, main data, chunk table  -> h2d(g)
     //   comp: [wait h2d(g), d2h(g-2)] main-data kernel, granule kernel     -> kern(g)
     //   down: [wait kern(g)] D2H PCM into the caller's buffer              -> d2h(g)
@@ -615,7 +635,7 @@ int mp3g_decode_streams_into(int device, uint32_t n_streams, const uint8_t* cons
     for (int i = 0; i < 2 && rc == MP3G_OK; i++) {
       const bool ok = B->arena[i].reserve(b_gran + b_jobs + b_md + b_chunks) && B->d_gran[i].reserve(b_gran) &&
                       B->d_jobs[i].reserve(b_jobs) && B->d_md[i].reserve(b_md) && B->d_chunks[i].reserve(b_chunks) &&
-                      B->d_pcm[i].reserve(max_ng * MP3G_PCM_BYTES_PER_GRANULE);
+                      B->d_pcm[i].reserve(max_ng * bpg);
       if (!ok) rc = abi_fail(MP3G_ERR_DEVICE, "decode_streams_into: buffers");
     }
     if (rc == MP3G_OK && !B->d_coef.reserve(max_ng * MP3G_COEF_PER_GRANULE * sizeof(int16_t)))
@@ -624,12 +644,12 @@ int mp3g_decode_streams_into(int device, uint32_t n_streams, const uint8_t* cons
     hipStream_t up = B->up, comp = B->comp, down = B->down;
     // the caller's PCM buffer: pinned and 16-B aligned -> our copy kernel
     // writes it through its device address; anything else -> hipMemcpyAsync
-    int16_t* pcm_dev = nullptr;
+    uint8_t* pcm_dev = nullptr;
     {
       hipPointerAttribute_t pa;
       if ((reinterpret_cast<uintptr_t>(pcm) & 15u) == 0 && hipPointerGetAttributes(&pa, pcm) == hipSuccess &&
           pa.type == hipMemoryTypeHost && pa.devicePointer)
-        pcm_dev = static_cast<int16_t*>(pa.devicePointer);
+        pcm_dev = static_cast<uint8_t*>(pa.devicePointer);
       (void)hipGetLastError();  // (pageable memory: an "invalid value" to clear)
     }
     std::vector<ChunkDesc> chunks;
@@ -724,7 +744,7 @@ int mp3g_decode_streams_into(int device, uint32_t n_streams, const uint8_t* cons
       if (e == hipSuccess) e = hipStreamWaitEvent(comp, B->h2d[slot], 0);
       if (e == hipSuccess && gi >= 2) e = hipStreamWaitEvent(comp, B->d2h[slot], 0);
       if (e == hipSuccess && holes)
-        e = hipMemsetAsync(B->d_pcm[slot].p, 0, ng * MP3G_PCM_BYTES_PER_GRANULE, comp);
+        e = hipMemsetAsync(B->d_pcm[slot].p, 0, ng * bpg, comp);
       if (e != hipSuccess) {
         rc = abi_fail(MP3G_ERR_DEVICE, "decode_streams_into: H2D");
         break;
@@ -735,21 +755,22 @@ int mp3g_decode_streams_into(int device, uint32_t n_streams, const uint8_t* cons
                                    (mode_reads_to_count1(mode) ? MP3G_HUFF_ROWS_COUNT1 : 0u) | stage, comp);
       if (rc == MP3G_OK && !chunks.empty()) {
         const ZoneScratch zs{static_cast<uint32_t*>(B->d_zones.p), B->zone_cap};
-        rc = plan_launch(mode & ~(uint32_t)MP3G_FLAG_HOT_STATS, static_cast<const ChunkDesc*>(B->d_chunks[slot].p),
-                         (uint32_t)chunks.size(), static_cast<const mp3g_granule*>(B->d_gran[slot].p),
-                         static_cast<const int16_t*>(B->d_coef.p), nullptr, nullptr,
-                         static_cast<int16_t*>(B->d_pcm[slot].p), &zs, comp);
+        // (planar output: the group's chunk table carries each stream's
+        // group-local first granule and its decoded count, as plan_chunks
+        // fills them, so the planes lie inside the stream's range of d_pcm)
+        rc = plan_launch_out(mode & ~(uint32_t)MP3G_FLAG_HOT_STATS, static_cast<const ChunkDesc*>(B->d_chunks[slot].p),
+                             (uint32_t)chunks.size(), static_cast<const mp3g_granule*>(B->d_gran[slot].p),
+                             static_cast<const int16_t*>(B->d_coef.p), nullptr, nullptr, B->d_pcm[slot].p, out_format,
+                             &zs, comp);
       }
       if (rc) break;
       e = hipEventRecord(B->kern[slot], comp);
       // down
       if (e == hipSuccess) e = hipStreamWaitEvent(down, B->kern[slot], 0);
       if (e == hipSuccess && pcm_dev)
-        e = launch_copy_out(B->d_pcm[slot].p, pcm_dev + G0 * (MP3G_PCM_BYTES_PER_GRANULE / sizeof(int16_t)),
-                            ng * MP3G_PCM_BYTES_PER_GRANULE, 8 * B->down_cus, down);
+        e = launch_copy_out(B->d_pcm[slot].p, pcm_dev + G0 * bpg, ng * bpg, 8 * B->down_cus, down);
       else if (e == hipSuccess)
-        e = hipMemcpyAsync(pcm + G0 * (MP3G_PCM_BYTES_PER_GRANULE / sizeof(int16_t)), B->d_pcm[slot].p,
-                           ng * MP3G_PCM_BYTES_PER_GRANULE, hipMemcpyDeviceToHost, down);
+        e = hipMemcpyAsync(pcm + G0 * bpg, B->d_pcm[slot].p, ng * bpg, hipMemcpyDeviceToHost, down);
       if (e == hipSuccess) e = hipEventRecord(B->d2h[slot], down);
       if (e != hipSuccess) rc = abi_fail(MP3G_ERR_DEVICE, "decode_streams_into: D2H");
       trace.mark("enqueue", gi);

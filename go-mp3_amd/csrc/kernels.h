@@ -80,7 +80,7 @@ hipError_t zone_scratch_init(void* p, uint32_t cap);
 // its hot-granule work to the scratch's counters (the other kernels ignore both).
 // out_format: MP3G_OUT_* -- d_out holds int16 or float32 samples accordingly;
 // the one-wave kernels (fast v3, exact v4) have an instantiation per format,
-// v2 writes s16 only (hipErrorInvalidValue otherwise).
+// v2 writes s16 stereo only (hipErrorInvalidValue otherwise).
 hipError_t launch_granule(int variant, const ChunkDesc* d_chunks, uint32_t n_chunks,
                           const mp3g_granule* d_gran, const int16_t* d_coef,
                           const mp3g_state* d_state_in, mp3g_state* d_state_out, void* d_out,

@@ -137,7 +137,7 @@ hipError_t launch_granule(int variant, const ChunkDesc* d_chunks, uint32_t n_chu
                        hot_stats, stream);
   if (variant == kVariantExact4)
     return launch_wexact(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_out, out_format, stream);
-  if (out_format != MP3G_OUT_S16) return hipErrorInvalidValue;  // (v2 has no float output)
+  if (out_format != MP3G_OUT_S16) return hipErrorInvalidValue;  // (v2 writes s16 stereo only)
   hipLaunchKernelGGL(v2::granule_fused_kernel, dim3(n_chunks), dim3(256), 0, stream, d_chunks,
                      d_gran, d_coef, d_state_in, d_state_out, static_cast<int16_t*>(d_out));
   return hipGetLastError();

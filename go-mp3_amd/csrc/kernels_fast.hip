@@ -133,6 +133,12 @@ hipError_t launch_fast(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_
     case MP3G_OUT_F32_PLANAR:
       return launch_fast_fmt<MP3G_OUT_F32_PLANAR>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
                                                   zones, hot_stats, stream);
+    case MP3G_OUT_S16_MONO:
+      return launch_fast_fmt<MP3G_OUT_S16_MONO>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
+                                                zones, hot_stats, stream);
+    case MP3G_OUT_F32_MONO:
+      return launch_fast_fmt<MP3G_OUT_F32_MONO>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
+                                                zones, hot_stats, stream);
   }
   return hipErrorInvalidValue;
 }
@@ -155,6 +161,12 @@ hipError_t launch_wexact(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3
     case MP3G_OUT_F32_PLANAR:
       return launch_wexact_fmt<MP3G_OUT_F32_PLANAR>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
                                                     stream);
+    case MP3G_OUT_S16_MONO:
+      return launch_wexact_fmt<MP3G_OUT_S16_MONO>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
+                                                  stream);
+    case MP3G_OUT_F32_MONO:
+      return launch_wexact_fmt<MP3G_OUT_F32_MONO>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
+                                                  stream);
   }
   return hipErrorInvalidValue;
 }

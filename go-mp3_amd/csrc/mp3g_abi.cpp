@@ -457,6 +457,8 @@ size_t mp3g_out_bytes_per_granule(uint32_t out_format) {
     case MP3G_OUT_S16: return MP3G_PCM_BYTES_PER_GRANULE;
     case MP3G_OUT_F32:
     case MP3G_OUT_F32_PLANAR: return 2 * MP3G_PCM_BYTES_PER_GRANULE;
+    case MP3G_OUT_S16_MONO: return MP3G_PCM_BYTES_PER_GRANULE / 2;
+    case MP3G_OUT_F32_MONO: return MP3G_PCM_BYTES_PER_GRANULE;
   }
   return 0;
 }
@@ -473,7 +475,7 @@ int mp3g_plan_execute_out(mp3g_plan* p, const mp3g_granule* d_gran, const int16_
   if (!mp3g_out_bytes_per_granule(out_format)) return fail(MP3G_ERR_INVALID_ARGUMENT, "unknown output format");
   if (!p) return fail(MP3G_ERR_INVALID_ARGUMENT, "null plan");
   if (out_format != MP3G_OUT_S16 && plan_variant(p->mode) == kVariantV2)
-    return fail(MP3G_ERR_UNSUPPORTED, "float output needs the one-wave kernels (no MP3G_FLAG_KERNEL_V2)");
+    return fail(MP3G_ERR_UNSUPPORTED, "this output format needs the one-wave kernels (no MP3G_FLAG_KERNEL_V2)");
   if (out_format == MP3G_OUT_F32_PLANAR) {
     // a plane pair is addressed with 31-bit byte offsets (granule_fast.hip store_pcm_f32)
     for (const ChunkDesc& c : p->chunks)

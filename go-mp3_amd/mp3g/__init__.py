@@ -46,8 +46,12 @@ STATE_IN, STATE_OUT = 1, 2
 MP3G_PCM_BYTES_PER_GRANULE = 2304  # include/mp3g.h: 576 stereo s16 samples
 # output formats (include/mp3g.h MP3G_OUT_*): s16 [n, 576, 2]; float32 in the
 # same order; float32 planar -- stream (first F, n granules) owns floats
-# [F * 1152, (F + n) * 1152), plane ch at F * 1152 + ch * n * 576
-OUT_S16, OUT_F32, OUT_F32_PLANAR = 0, 1, 2
+# [F * 1152, (F + n) * 1152), plane ch at F * 1152 + ch * n * 576; the mono
+# downmixes [n, 576]: (L + R) >> 1 of the s16 samples, (fL + fR) * 0.5f of the
+# float samples (a mono granule: channel 0 as it is)
+OUT_S16, OUT_F32, OUT_F32_PLANAR, OUT_S16_MONO, OUT_F32_MONO = 0, 1, 2, 3, 4
+_OUT_INT16 = (OUT_S16, OUT_S16_MONO)  # (the others hold float32)
+_OUT_MONO = (OUT_S16_MONO, OUT_F32_MONO)
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "invalid granule", 3: "no device", 4: "device error",
           5: "out of memory", 6: "parse error", 7: "eof", 8: "unsupported", 9: "no Xing/Info header",
@@ -131,6 +135,9 @@ def lib():
         L.mp3g_huffman_stage_flags.restype = u32
         L.mp3g_decode_streams.argtypes = [C.c_int, u32, vp, vp, C.c_int, u32, C.POINTER(vp), C.POINTER(u64),
                                           vp, vp]
+        if hasattr(L, "mp3g_decode_streams_into_out"):  # (an older build through MP3G_LIB: A/B runs)
+            L.mp3g_decode_streams_into_out.argtypes = [C.c_int, u32, vp, vp, C.c_int, u32, u32, vp, u32, u64,
+                                                       C.POINTER(u64), vp, vp]
         L.mp3g_decode_streams_into.argtypes = [C.c_int, u32, vp, vp, C.c_int, u32, u32, vp, u64, C.POINTER(u64),
                                                vp, vp]
         L.mp3g_release_cached_buffers.argtypes = []
@@ -188,7 +195,7 @@ def validate(granules, coeffs):
 
 
 def out_bytes_per_granule(out_format):
-    """Output bytes per granule of OUT_* (2304 / 4608 / 4608); 0 for an unknown format."""
+    """Output bytes per granule of OUT_* (2304 / 4608 / 4608 / 1152 / 2304); 0 for an unknown format."""
     return int(lib().mp3g_out_bytes_per_granule(int(out_format)))
 
 
@@ -210,9 +217,11 @@ def decode_host(granules, coeffs, streams=None, state_in=None, state_out=None, m
 
     granules: GRANULE_DTYPE[n]; coeffs: int16[n, 2, 576]; streams: STREAM_DTYPE[s]
     (default: one stream covering everything).  Returns (pcm, state_out): pcm is
-    int16[n, 576, 2] (OUT_S16), float32[n, 576, 2] (OUT_F32) or a flat float32
+    int16[n, 576, 2] (OUT_S16), float32[n, 576, 2] (OUT_F32), a flat float32
     array of n * 1152 (OUT_F32_PLANAR: planar_views(pcm, streams) gives each
-    stream's [2, n * 576]).  trunc(float * 32768) is the s16 sample.
+    stream's [2, n * 576]), or the mono downmix int16[n, 576] (OUT_S16_MONO) /
+    float32[n, 576] (OUT_F32_MONO).  trunc(float * 32768) is the s16 sample
+    (stereo formats).
     """
     granules = np.ascontiguousarray(granules, dtype=GRANULE_DTYPE)
     coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
@@ -230,7 +239,10 @@ def decode_host(granules, coeffs, streams=None, state_in=None, state_out=None, m
         _check(lib().mp3g_decode_host(device, _ptr(granules), _ptr(coeffs), n, _ptr(streams),
                                       len(streams), _ptr(state_in), _ptr(state_out), _ptr(pcm), mode))
         return pcm, state_out
-    pcm = np.zeros(n * 1152 if out_format == OUT_F32_PLANAR else (n, 576, 2), np.float32)
+    if out_format in _OUT_MONO:
+        pcm = np.zeros((n, 576), np.int16 if out_format == OUT_S16_MONO else np.float32)
+    else:
+        pcm = np.zeros(n * 1152 if out_format == OUT_F32_PLANAR else (n, 576, 2), np.float32)
     _check(lib().mp3g_decode_host_out(device, _ptr(granules), _ptr(coeffs), n, _ptr(streams), len(streams),
                                       _ptr(state_in), _ptr(state_out), _ptr(pcm), int(out_format), mode))
     return pcm, state_out
@@ -453,10 +465,11 @@ def decode_streams_tensor(datas, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, n_t
     current torch stream -- no PCM comes back to the host.  Returns when the
     kernels are done (the plan and the input buffers are released then).
 
-    Returns (out, views, streams, end_status).  out: a float32 (OUT_S16:
-    int16) tensor of 1152 samples per granule on cuda:device; views[k] is
-    stream k's part of it -- [2, T] for OUT_F32_PLANAR, [T, 2] for the
-    interleaved formats, T = 576 * n_granules.  streams / end_status as
+    Returns (out, views, streams, end_status).  out: a float32 (OUT_S16 /
+    OUT_S16_MONO: int16) tensor of 1152 samples per granule (the mono formats:
+    576) on cuda:device; views[k] is stream k's part of it, a slice --
+    [2, T] for OUT_F32_PLANAR, [T, 2] for the interleaved formats, [T] for
+    the mono formats, T = 576 * n_granules.  streams / end_status as
     decode_streams.  No gapless trimming: slice a view with LameInfo.trim."""
     import torch
     if not out_bytes_per_granule(out_format):
@@ -464,7 +477,8 @@ def decode_streams_tensor(datas, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, n_t
     s = scan_streams(datas, n_threads=n_threads)
     streams, n = s["streams"], len(s["granules"])
     dev = torch.device("cuda", device)
-    out = torch.empty(n * 1152, dtype=torch.int16 if out_format == OUT_S16 else torch.float32, device=dev)
+    per = 576 if out_format in _OUT_MONO else 1152  # samples per granule slot
+    out = torch.empty(n * per, dtype=torch.int16 if out_format in _OUT_INT16 else torch.float32, device=dev)
     if n:
         d_g = torch.from_numpy(s["granules"].view(np.uint8)).to(dev)
         d_j = torch.from_numpy(s["jobs"].view(np.uint8)).to(dev)
@@ -482,18 +496,22 @@ def decode_streams_tensor(datas, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, n_t
         plan.close()
     if out_format == OUT_F32_PLANAR:
         views = planar_views(out, streams)
+    elif out_format in _OUT_MONO:
+        views = [out[int(f) * 576:(int(f) + int(k)) * 576]
+                 for f, k in zip(streams["first_granule"], streams["n_granules"])]
     else:
         views = [out[int(f) * 1152:(int(f) + int(k)) * 1152].reshape(int(k) * 576, 2)
                  for f, k in zip(streams["first_granule"], streams["n_granules"])]
     return out, views, streams, s["end_status"]
 
 
-def _host_buffer(out, want_int16):
+def _host_buffer(out, want_int16, want_float32=False):
     """(pointer, size in bytes) of a caller's writable, C-contiguous HOST
     buffer -- a numpy array or a CPU torch tensor (pinned or not).  The
     library writes host memory through the pointer, so device tensors,
     non-contiguous views and read-only arrays are refused, and so is any
-    dtype but int16 where the PCM is addressed in samples."""
+    dtype but int16 (or float32, for the float output formats) where the PCM
+    is addressed in samples."""
     if hasattr(out, "data_ptr"):  # torch.Tensor
         if out.device.type != "cpu":
             raise ValueError("output buffer must be in host memory (got a %s tensor)" % out.device)
@@ -501,6 +519,8 @@ def _host_buffer(out, want_int16):
             raise ValueError("output buffer must be contiguous")
         if want_int16 and str(out.dtype) != "torch.int16":
             raise ValueError("output buffer must be int16 (got %s)" % out.dtype)
+        if want_float32 and str(out.dtype) != "torch.float32":
+            raise ValueError("output buffer must be float32 (got %s)" % out.dtype)
         return out.data_ptr(), out.numel() * out.element_size()
     a = out
     if not isinstance(a, np.ndarray):
@@ -509,24 +529,36 @@ def _host_buffer(out, want_int16):
         raise ValueError("output buffer must be C-contiguous and writable")
     if want_int16 and a.dtype != np.int16:
         raise ValueError("output buffer must be int16 (got %s)" % a.dtype)
+    if want_float32 and a.dtype != np.float32:
+        raise ValueError("output buffer must be float32 (got %s)" % a.dtype)
     return a.ctypes.data, a.nbytes
 
 
-def decode_streams_into(datas, out, mode=MODE_EXACT, n_threads=0, n_groups=0, device=0):
-    """Pipelined bitstreams-in, PCM-out (mp3g_decode_streams_into): groups of
-    streams, each group's host scan overlapping the previous group's
-    transfers and kernels.  `out` is a writable, C-contiguous int16 host
-    buffer (numpy array or a pinned CPU torch tensor) of at least
-    1152 * (total granules) samples; the layout comes from a header-only
-    pre-pass (streams[k].first_granule).  Returns (n_granules, streams, end_status)."""
+def decode_streams_into(datas, out, mode=MODE_EXACT, n_threads=0, n_groups=0, device=0, out_format=OUT_S16):
+    """Pipelined bitstreams-in, PCM-out (mp3g_decode_streams_into_out): groups
+    of streams, each group's host scan overlapping the previous group's
+    transfers and kernels.  `out` is a writable, C-contiguous host buffer
+    (numpy array or a pinned CPU torch tensor) of the format's dtype -- int16
+    for OUT_S16 / OUT_S16_MONO, float32 otherwise -- and of at least
+    out_bytes_per_granule(out_format) * (total granules) bytes; the layout
+    comes from a header-only pre-pass: stream k starts at granule slot
+    streams[k].first_granule.  Returns (n_granules, streams, end_status)."""
+    bpg = out_bytes_per_granule(out_format)
+    if not bpg:
+        raise Mp3gError(1, "unknown output format")
     bufs, ptrs, lens = _stream_args(datas)
     streams = np.zeros(len(datas), STREAM_DTYPE)
     status = np.zeros(max(1, len(datas)), np.int32)
     n = C.c_uint64()
-    ptr, nbytes = _host_buffer(out, want_int16=True)
-    cap = nbytes // MP3G_PCM_BYTES_PER_GRANULE
-    _check(lib().mp3g_decode_streams_into(device, len(datas), ptrs, lens, n_threads, mode, n_groups,
-                                          C.c_void_p(ptr), cap, C.byref(n), _ptr(streams), _ptr(status)))
+    ptr, nbytes = _host_buffer(out, want_int16=out_format in _OUT_INT16, want_float32=out_format not in _OUT_INT16)
+    cap = nbytes // bpg
+    if out_format == OUT_S16 and not hasattr(lib(), "mp3g_decode_streams_into_out"):  # (an older build: A/B runs)
+        _check(lib().mp3g_decode_streams_into(device, len(datas), ptrs, lens, n_threads, mode, n_groups,
+                                              C.c_void_p(ptr), cap, C.byref(n), _ptr(streams), _ptr(status)))
+        return n.value, streams, status[:len(datas)]
+    _check(lib().mp3g_decode_streams_into_out(device, len(datas), ptrs, lens, n_threads, mode, n_groups,
+                                              C.c_void_p(ptr), int(out_format), cap, C.byref(n), _ptr(streams),
+                                              _ptr(status)))
     return n.value, streams, status[:len(datas)]
 
 

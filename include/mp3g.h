@@ -47,7 +47,9 @@ extern "C" {
  *    launches share, so executions of one plan must be stream-ordered.
  *    (Compatible additions since: the diagnostic mp3g_debug_clock_probe;
  *    float32 PCM output -- MP3G_OUT_*, mp3g_out_bytes_per_granule,
- *    mp3g_plan_execute_out and mp3g_decode_host_out.) */
+ *    mp3g_plan_execute_out and mp3g_decode_host_out; the mono downmix
+ *    formats MP3G_OUT_S16_MONO / MP3G_OUT_F32_MONO and
+ *    mp3g_decode_streams_into_out.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -115,8 +117,9 @@ typedef struct mp3g_granule {
  * (frame.go:134: granule gr at byte 2304*gr; mono duplicated, frame.go:671-678). */
 #define MP3G_PCM_BYTES_PER_GRANULE (MP3G_LINES * 2 * 2)
 
-/* ---- output formats (mp3g_plan_execute_out / mp3g_decode_host_out) -------
- * The sample value is the same in every format and both modes.  With
+/* ---- output formats (mp3g_plan_execute_out / mp3g_decode_host_out /
+ *      mp3g_decode_streams_into_out) ---------------------------------------
+ * The stereo sample value is the same in every format and both modes.  With
  * t = sum * 32767 as the window stage computes it (frame.go:649-662),
  *   s16:   (int16)trunc(clamp(t, -32767, 32767))        (frame.go:663-669)
  *   float: f = clamp(t, -32767, 32767) * 2^-15          (no truncation)
@@ -124,14 +127,31 @@ typedef struct mp3g_granule {
  * |f| <= 32767/32768.  Mono granules write channel 0 to both channels / planes
  * (frame.go:671-678).  The exported state does not depend on the format.
  * MP3G_OUT_F32_PLANAR needs streams that do not overlap, each of fewer than
- * MP3G_PLANAR_MAX_GRANULES granules (MP3G_ERR_UNSUPPORTED otherwise). */
+ * MP3G_PLANAR_MAX_GRANULES granules (MP3G_ERR_UNSUPPORTED otherwise).
+ *
+ * The mono formats hold one downmixed channel: sample i of granule g at index
+ * 576 g + i, so a stream's samples are contiguous and in time order.
+ *   MP3G_OUT_S16_MONO: m = (L + R) >> 1 on the s16 samples (L, R) that
+ *     MP3G_OUT_S16 of the same plan writes -- an arithmetic shift (floor) of
+ *     the 32-bit sum.  Exact mode stays a pure function of the reference's
+ *     bytes; fast mode's +-1 per channel gives floors at most 1 apart.
+ *   MP3G_OUT_F32_MONO: m = (fL + fR) * 0.5f on the float samples (fL, fR) that
+ *     MP3G_OUT_F32 writes -- one float32 add rounded to nearest, then the
+ *     exact halving; |m| <= 32767/32768.
+ * A mono granule gives m = L, or m = fL bit for bit.  The two mono formats
+ * round at different points: trunc(m * 32768) of the float sample is NOT
+ * promised to equal the MP3G_OUT_S16_MONO sample (the identity above holds for
+ * the stereo formats only). */
 #define MP3G_OUT_S16        0u /* int16 [n_granules][576][2]: the layout above             */
 #define MP3G_OUT_F32        1u /* float [n_granules][576][2]: same order, float32          */
 #define MP3G_OUT_F32_PLANAR 2u /* float; stream s (first F, n granules) owns floats
                                   [F*1152, (F+n)*1152): plane ch at F*1152 + ch*n*576,
                                   n*576 samples, in time order                             */
+#define MP3G_OUT_S16_MONO   3u /* int16 [n_granules][576]: (L + R) >> 1                       */
+#define MP3G_OUT_F32_MONO   4u /* float [n_granules][576]: (fL + fR) * 0.5f                   */
 #define MP3G_PLANAR_MAX_GRANULES 900000u /* (a plane pair is addressed with 31-bit byte offsets) */
-/* Output bytes per granule of a format: 2304 / 4608 / 4608; 0 = unknown format. */
+/* Output bytes per granule of a format: 2304 / 4608 / 4608 / 1152 / 2304;
+ * 0 = unknown format. */
 size_t mp3g_out_bytes_per_granule(uint32_t out_format);
 
 /* ---- cross-granule DSP state (reference Frame.store / Frame.vVec) ------- */
@@ -223,10 +243,11 @@ int mp3g_plan_execute(mp3g_plan* plan, const mp3g_granule* d_granules,
 /* The same with the output format chosen per call (MP3G_OUT_*): d_out holds
  * mp3g_out_bytes_per_granule(out_format) bytes per granule slot.
  * mp3g_plan_execute is the MP3G_OUT_S16 case.  An unknown format is
- * MP3G_ERR_INVALID_ARGUMENT (checked before any device call); a float format
- * on an MP3G_FLAG_KERNEL_V2 plan is MP3G_ERR_UNSUPPORTED (the one-wave kernels,
- * fast v3 and exact v4, write floats straight from the window's registers;
- * the cross-check kernel stays s16).  No reference counterpart: go-mp3's
+ * MP3G_ERR_INVALID_ARGUMENT (checked before any device call); any format but
+ * MP3G_OUT_S16 on an MP3G_FLAG_KERNEL_V2 plan is MP3G_ERR_UNSUPPORTED (the
+ * one-wave kernels, fast v3 and exact v4, write floats and the mono downmix
+ * straight from the window's registers; the cross-check kernel stays s16
+ * stereo).  No reference counterpart: go-mp3's
  * Decode returns s16 bytes only (frame.go:121-137). */
 int mp3g_plan_execute_out(mp3g_plan* plan, const mp3g_granule* d_granules,
                           const int16_t* d_coeffs, const mp3g_state* d_state_in,
@@ -409,6 +430,19 @@ int mp3g_decode_streams_into(int device, uint32_t n_streams, const uint8_t* cons
                              int n_threads, uint32_t mode, uint32_t n_groups, int16_t* pcm,
                              uint64_t pcm_cap_granules, uint64_t* n_granules, mp3g_stream* streams,
                              int* end_status);
+
+/* The same with an output format (MP3G_OUT_*, all of them): `out` holds
+ * out_cap_granules * mp3g_out_bytes_per_granule(out_format) bytes, and stream
+ * k's output starts at byte streams[k].first_granule *
+ * mp3g_out_bytes_per_granule(out_format) of it (MP3G_OUT_F32_PLANAR: its two
+ * planes inside that range, as above).  A stream that ends early leaves the
+ * rest of its range zero in every format.  An unknown format is
+ * MP3G_ERR_INVALID_ARGUMENT before any device call.
+ * mp3g_decode_streams_into is the MP3G_OUT_S16 case. */
+int mp3g_decode_streams_into_out(int device, uint32_t n_streams, const uint8_t* const* datas, const size_t* lens,
+                                 int n_threads, uint32_t mode, uint32_t n_groups, void* out, uint32_t out_format,
+                                 uint64_t out_cap_granules, uint64_t* n_granules, mp3g_stream* streams,
+                                 int* end_status);
 
 /* mp3g_decode_streams_into keeps its staging (page-locked) and device
  * buffers per device between calls; this frees them (idle sets only). */

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Plan.execute time per output format (s16, float32 interleaved, float32
-planar) on the c3 workload, fast and exact mode, in one process.
+planar, s16 mono downmix, float32 mono downmix) on the c3 workload, fast and
+exact mode, in one process.
 
 The batch is bench.py's c3 (1,024 independently seeded streams x 1,024 frames,
 synth.encode_batch seeds 1..1024).  The formats alternate inside every round
-(s16, f32, planar, s16, ...), each window of --steps launches bracketed by a
+(s16, f32, planar, s16 mono, f32 mono, s16, ...), each window of --steps launches bracketed by a
 device synchronise and timed with HIP events on the launch stream; a format's
 time is the median of its windows.  Writes one JSON line to
 profiles/outfmt_c3.json (and prints it): ms per mode and format, the bytes a
@@ -47,7 +48,8 @@ def main():
     n = len(g)
     d_g = torch.from_numpy(g.view(np.uint8)).to(dev)
     d_c = torch.from_numpy(c.view(np.uint8).reshape(-1)).to(dev)
-    fmts = (("s16", mp3g.OUT_S16), ("f32", mp3g.OUT_F32), ("f32_planar", mp3g.OUT_F32_PLANAR))
+    fmts = (("s16", mp3g.OUT_S16), ("f32", mp3g.OUT_F32), ("f32_planar", mp3g.OUT_F32_PLANAR),
+            ("s16_mono", mp3g.OUT_S16_MONO), ("f32_mono", mp3g.OUT_F32_MONO))
     d_out = {name: torch.empty(n * mp3g.out_bytes_per_granule(f), dtype=torch.uint8, device=dev) for name, f in fmts}
     st = torch.cuda.current_stream(dev)
     h = st.cuda_stream
@@ -85,6 +87,13 @@ def main():
     f32 = d_out["f32"].view(torch.float32)
     q = torch.trunc(f32 * 32768.0).to(torch.int16)
     res["f32_matches_s16"] = bool(torch.equal(q, d_out["s16"].view(torch.int16)))
+    # and the mono formats are the downmix of the stereo ones: (L + R) >> 1, (fL + fR) * 0.5f
+    lr = d_out["s16"].view(torch.int16).view(-1, 2).to(torch.int32)
+    res["s16_mono_matches_s16"] = bool(torch.equal(((lr[:, 0] + lr[:, 1]) >> 1).to(torch.int16),
+                                                   d_out["s16_mono"].view(torch.int16)))
+    del lr, q
+    f2 = f32.view(-1, 2)
+    res["f32_mono_matches_f32"] = bool(torch.equal((f2[:, 0] + f2[:, 1]) * 0.5, d_out["f32_mono"].view(torch.float32)))
     line = json.dumps(res)
     print(line)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
@@ -92,6 +101,8 @@ def main():
         fh.write(line + "\n")
     if not res["f32_matches_s16"]:
         raise SystemExit("outfmt_time: float output does not quantise to the s16 output")
+    if not (res["s16_mono_matches_s16"] and res["f32_mono_matches_f32"]):
+        raise SystemExit("outfmt_time: a mono output is not the downmix of its stereo format")
 
 
 if __name__ == "__main__":

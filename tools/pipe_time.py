@@ -1,9 +1,15 @@
 """Timing of the pipelined batch drop-in (mp3g_decode_streams_into) at c3
 (VERDICT r04 item 3), beside what bounds it: the host scan alone and the PCIe
 rates of the same bytes (pinned, one direction at a time and both at once).
-GPU box:  python tools/pipe_time.py [repeats] [n_groups ...]
+GPU box:  python tools/pipe_time.py [repeats] [n_groups ...] [--formats s16,s16_mono,f32_mono] [--out FILE.json]
+--formats: the output formats of mp3g_decode_streams_into_out to time, one
+after the other in this process (s16, f32, f32_planar, s16_mono, f32_mono;
+default s16), each with the PCIe time of its own output bytes beside it;
+--out: the numbers as one JSON line.
 (under rocprofv3 --kernel-trace --memory-copy-trace for the timeline;
 MP3G_PIPE_TRACE=1 prints the library's per-group host timestamps)."""
+import argparse
+import json
 import os
 import sys
 import time
@@ -19,8 +25,16 @@ from mp3g import synth  # noqa: E402
 
 
 def main():
-    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-    groups = [int(a) for a in sys.argv[2:]] or [0]
+    ap = argparse.ArgumentParser()
+    ap.add_argument("repeats", nargs="?", type=int, default=3)
+    ap.add_argument("n_groups", nargs="*", type=int)
+    ap.add_argument("--formats", default="s16")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    reps, groups = a.repeats, a.n_groups or [0]
+    known = {"s16": mp3g.OUT_S16, "f32": mp3g.OUT_F32, "f32_planar": mp3g.OUT_F32_PLANAR,
+             "s16_mono": mp3g.OUT_S16_MONO, "f32_mono": mp3g.OUT_F32_MONO}
+    fmts = [(f, known[f]) for f in a.formats.split(",")]
     n_streams, n_frames = 1024, 1024
     t = time.perf_counter()
     with ThreadPoolExecutor(16) as ex:
@@ -57,23 +71,50 @@ def main():
     print(f"PCIe: D2H {hp.numel() * 2 / 1e9:.2f} GB {d2h * 1e3:.1f} ms = {hp.numel() * 2 / d2h / 1e9:.1f} GB/s; "
           f"H2D {inb / 1e9:.2f} GB {h2d * 1e3:.1f} ms = {inb / h2d / 1e9:.1f} GB/s; both at once {both * 1e3:.1f} ms",
           flush=True)
-    ref = None
-    for G in groups:
-        times = []
-        for _ in range(reps):
+    res = {"tool": "tools/pipe_time.py", "workload": f"c3: {n_streams} streams x {n_frames} frames", "granules": n,
+           "repeats": reps, "mode": "fast", "host_scan_ms": round(s["scan_s"] * 1e3, 1),
+           "pcie_s16": {"d2h_ms": round(d2h * 1e3, 1), "h2d_ms": round(h2d * 1e3, 1), "both_ms": round(both * 1e3, 1)},
+           "formats": {}}
+    del hp, d_p
+    for name, fmt in fmts:
+        bpg = mp3g.out_bytes_per_granule(fmt)
+        dt = torch.int16 if fmt in (mp3g.OUT_S16, mp3g.OUT_S16_MONO) else torch.float32
+        hp = torch.empty(n * bpg // (2 if dt == torch.int16 else 4), dtype=dt).pin_memory()
+        # the PCIe time of this format's output bytes alone
+        d_p = torch.empty_like(hp, device=dev)
+        for _ in range(2):
+            torch.cuda.synchronize()
             t = time.perf_counter()
-            n_p, _, st = mp3g.decode_streams_into(datas, hp, mode=mp3g.MODE_FAST, n_threads=16, n_groups=G)
-            times.append(time.perf_counter() - t)
-            assert n_p == n and all(x == 7 for x in st)
-        same = None
-        h = hp[::4099].clone()
-        if ref is None:
-            ref = h
-        else:
-            same = bool(torch.equal(h, ref))
-        print(f"decode_streams_into n_groups={G}: " + " ".join(f"{x * 1e3:.1f}" for x in times) +
-              f" ms  ({n // 2 / min(times[1:] or times):.3e} frames/s best after the first; PCM same as first: {same})",
-              flush=True)
+            hp.copy_(d_p, non_blocking=True)
+            torch.cuda.synchronize()
+            d2h = time.perf_counter() - t
+        del d_p
+        print(f"{name}: {n * bpg / 1e9:.2f} GB of output, D2H alone {d2h * 1e3:.1f} ms", flush=True)
+        res["formats"][name] = {"out_gb": round(n * bpg / 1e9, 3), "d2h_alone_ms": round(d2h * 1e3, 1), "ms": {}}
+        ref = None
+        for G in groups:
+            times = []
+            for _ in range(reps):
+                t = time.perf_counter()
+                n_p, _, st = mp3g.decode_streams_into(datas, hp, mode=mp3g.MODE_FAST, n_threads=16, n_groups=G,
+                                                      out_format=fmt)
+                times.append(time.perf_counter() - t)
+                assert n_p == n and all(x == 7 for x in st)
+            same = None
+            h = hp[::4099].clone()
+            if ref is None:
+                ref = h
+            else:
+                same = bool(torch.equal(h, ref))
+            res["formats"][name]["ms"][str(G)] = [round(x * 1e3, 1) for x in times]
+            print(f"decode_streams_into {name} n_groups={G}: " + " ".join(f"{x * 1e3:.1f}" for x in times) +
+                  f" ms  ({n // 2 / min(times[1:] or times):.3e} frames/s best after the first; PCM same as first: {same})",
+                  flush=True)
+        del hp
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(json.dumps(res) + "\n")
 
 
 if __name__ == "__main__":
