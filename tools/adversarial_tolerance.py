@@ -12,9 +12,11 @@ concentration, alternating subbands, sparse spikes of L1 = 64 split over
 oracle over the non-clipped samples, per pattern, for
 
   synth : the standalone polyphase kernel (S given directly as float32 lines);
-  fused : the fused fast kernel (int16 coefficients; global_gain per stream
-          set to the largest value that keeps every granule under the limits,
-          from the oracle's exact S at gain 210 scaled by 2^((gg-210)/4)).
+  fused : the fused fast kernel (int16 coefficients; amplitude and
+          global_gain per stream chosen to put it just under its governing
+          limit, from the oracle's exact S at gain 210 scaled by
+          2^((gg-210)/4): tests/fast_edge_inputs.py, the builder the tests of
+          tests/test_gpu_fast_threshold.py use, here at a larger size).
 
   python tools/adversarial_tolerance.py [--batches 8] [--out gpurun_out/adv.json]
 
@@ -33,8 +35,20 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("go-mp3_amd", "oracle", "tests"):
     sys.path.insert(0, os.path.join(REPO, p))
 
-HOT_S, HOT_L1 = 4.0, 64.0  # granule_fast.hip kHotS / kHotL1 (round 3: kHotS = 8)
+HOT_S, HOT_L1 = None, None  # granule_fast.hip kHotS / kHotL1: mp3g.FAST_HOT_S / FAST_HOT_L1 unless given
 EDGE = 1.0 - 1e-6  # just under the limit
+
+
+# the fused half's patterns: (name, kind, variant, amplitudes searched) of
+# tests/fast_edge_inputs.py's edge_batch (the round-4 names first)
+FUSED_PATTERNS = [("rand15", "rand", "long", None), ("rand1", "rand", "long", (1,)), ("alt15", "alt", "long", None),
+                  ("altsb15", "altsb", "long", None), ("spike", "spike_zero", "long", None),
+                  ("spike+rand", "spike_rand", "long", None), ("low15", "low", "long", None),
+                  ("short_rand15", "rand", "short", None), ("p43edge", "p43edge", "long", None),
+                  ("mixed_rand", "rand", "mixed", None), ("ms_rand", "rand", "ms", None),
+                  ("mono_low", "low", "mono", None), ("bandgain_rand", "rand", "bandgain", None),
+                  ("bandgain_short_rand", "rand", "bandgain_short", None),
+                  ("bandgain_short_altsb", "altsb", "bandgain_short", None)]
 
 
 def nwin_signs():
@@ -133,13 +147,14 @@ def main():
     ap.add_argument("--granules", type=int, default=8192, help="per batch and pattern")
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None, help="synth | fused")
-    ap.add_argument("--hot-s", type=float, default=HOT_S,
+    ap.add_argument("--hot-s", type=float, default=None,
                     help="kHotS of the library under test (a build with -DMP3G_HOT_S=..., loaded via MP3G_LIB)")
-    ap.add_argument("--hot-l1", type=float, default=HOT_L1, help="kHotL1 of the library under test")
+    ap.add_argument("--hot-l1", type=float, default=None, help="kHotL1 of the library under test")
     args = ap.parse_args()
-    HOT_S, HOT_L1 = args.hot_s, args.hot_l1
     import torch  # noqa: F401  (shared HIP runtime)
     import mp3g
+    HOT_S = mp3g.FAST_HOT_S if args.hot_s is None else args.hot_s
+    HOT_L1 = mp3g.FAST_HOT_L1 if args.hot_l1 is None else args.hot_l1
     import oracle
     from mp3g import synth
     from test_gpu_synth import run_synth
@@ -183,77 +198,37 @@ def main():
             print("synth", key, agg, f"{time.time() - t0:.0f}s", flush=True)
         res["synth_worst"] = {"max_dpcm": worst[0], "pattern": worst[1]}
     if args.only in (None, "fused"):
+        # the inputs of tests/test_gpu_fast_threshold.py at this tool's size
+        # (tests/fast_edge_inputs.py: amplitude and global_gain per stream,
+        # every stream just under its governing bound)
+        import fast_edge_inputs as fe
         worst = (-1, None)
-        i = np.arange(576)
-        for kind in ("rand15", "rand1", "alt15", "altsb15", "spike", "spike+rand", "low15", "short_rand15"):
-            agg = {"granules": 0, "max_dpcm": 0, "frac_diff": 0.0, "frac_clipped": 0.0, "hot_by_oracle_S": 0}
+        for name, kind, variant, amps in FUSED_PATTERNS:
+            agg = {"granules": 0, "max_dpcm": 0, "frac_diff": 0.0, "frac_clipped": 0.0, "hot_by_oracle_S": 0,
+                   "frac_diff_unclipped": 0.0, "min_ratio": 1.0}
             for b in range(args.batches):
                 ns = args.granules // 2
-                g, c, s = synth.synth_batch(ns, 1, seed=100 + b, p_is=0.0, p_ms=0.0, p_event=0.0)
+                g, c, s, info = fe.edge_batch(kind, variant, "under", n_streams=ns, frames=1, seed=100 + b,
+                                              amps=amps, hot_s=HOT_S, hot_l1=HOT_L1)
                 n = len(g)
-                g["header"] = synth.header(synth.MODE_STEREO)
-                for ch in range(2):
-                    C = g["ch"][:, ch]
-                    C["global_gain"] = 210
-                    C["scalefac_l"] = 0
-                    C["scalefac_s"] = 0
-                    C["preflag"] = 0
-                    C["subblock_gain"] = 0
-                    C["count1"] = 576
-                    if kind == "short_rand15":
-                        C["win_switch_flag"] = 1
-                        C["block_type"] = 2
-                        C["mixed_block_flag"] = 0
-                if kind in ("rand15", "short_rand15"):
-                    c[:] = rng.integers(-15, 16, size=(n, 2, 576))
-                elif kind == "rand1":
-                    c[:] = rng.integers(-1, 2, size=(n, 2, 576))
-                elif kind == "alt15":
-                    c[:] = np.where(i % 2 == 0, 15, -15)
-                elif kind == "altsb15":
-                    c[:] = np.where((i // 18) % 2 == 0, 15, -15)
-                elif kind == "low15":
-                    c[:] = 0
-                    c[:, :, :72] = rng.integers(-15, 16, size=(n, 2, 72))
-                else:
-                    c[:] = rng.integers(-2, 3, size=(n, 2, 576)) if kind == "spike+rand" else 0
-                    for gi in range(n):
-                        for ch in range(2):
-                            pos = rng.choice(576, size=3, replace=False)
-                            c[gi, ch, pos] = rng.choice([-8206, -5000, 3000, 8206], size=3)
-                c = c.astype(np.int16)
-                # exact S at gain 210; the largest gain per stream that keeps
-                # every granule of it fast (first test, or the second)
-                S0 = oracle.hybrid_streams(g, c, s).astype(np.float64).reshape(n, 2, 32, 18)
-                mx = np.abs(S0).reshape(n, -1).max(axis=1)
-                l1 = np.abs(S0).sum(axis=2).reshape(n, -1).max(axis=1)
-                per_s = np.repeat(np.arange(ns), 2)
-                mx_s = np.maximum.reduceat(mx, np.arange(0, n, 2))
-                l1_s = np.maximum.reduceat(l1, np.arange(0, n, 2))
-                # scale f = 2^((gg-210)/4): A allows f <= 8/mx, B allows f <= 64/l1
-                fmax = np.maximum(HOT_S / np.maximum(mx_s, 1e-30), HOT_L1 / np.maximum(l1_s, 1e-30))
-                gg = np.clip(210 + np.floor(4 * np.log2(fmax) - 1e-9), 0, 255).astype(np.int64)
-                for ch in range(2):
-                    g["ch"]["global_gain"][:, ch] = gg[per_s]
-                want = oracle.dsp_streams_mt(g, c, s, 16)
+                want = info["pcm"]
                 got, _ = run_plan(mp3g, g, c, s, mode=mp3g.MODE_FAST)
                 m, f, clip, per_g = measure(got, want)
-                S1 = oracle.hybrid_streams(g, c, s).reshape(n, 2, 32, 18)
-                hot = (np.abs(S1).reshape(n, -1).max(axis=1) > HOT_S) & \
-                      (np.abs(S1).sum(axis=2).reshape(n, -1).max(axis=1) > HOT_L1)
                 agg["granules"] += n
                 agg["max_dpcm"] = max(agg["max_dpcm"], m)
                 agg["frac_diff"] += f / args.batches
                 agg["frac_clipped"] += clip / args.batches
-                agg["hot_by_oracle_S"] += int(hot.sum())
+                agg["frac_diff_unclipped"] += f / max(1.0 - clip, 1e-30) / args.batches
+                agg["min_ratio"] = min(agg["min_ratio"], float(info["ratio"].min()))
+                agg["hot_by_oracle_S"] += int(info["hot"].sum())
                 if m > worst[0]:
                     gi = int(np.argmax(per_g))
                     st = gi - gi % 2
-                    worst = (m, kind)
+                    worst = (m, name)
                     np.savez(os.path.join(REPO, "gpurun_out", "adv_worst_fused.npz"), coeffs=c[st:st + 2],
                              granules=g[st:st + 2], want=want[st:st + 2], got=got[st:st + 2])
-            res["fused"][kind] = agg
-            print("fused", kind, agg, f"{time.time() - t0:.0f}s", flush=True)
+            res["fused"][name] = agg
+            print("fused", name, agg, f"{time.time() - t0:.0f}s", flush=True)
         res["fused_worst"] = {"max_dpcm": worst[0], "pattern": worst[1]}
     res["seconds"] = round(time.time() - t0, 1)
     print(json.dumps({k: res[k] for k in res if k.endswith("worst")}))
