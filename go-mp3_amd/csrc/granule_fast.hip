@@ -1027,7 +1027,12 @@ __device__ __forceinline__ void store_pcm_f32(int16_t* pcm, StreamGeom sg, uint3
 //   float: m = (fL + fR) * 0.5f on the float samples (one rounded add; the
 //          halving is exact)
 // A mono granule gives channel 0's sample as it is (wave-uniform branch).
-constexpr bool fmt_is_mono(int fmt) { return fmt == (int)MP3G_OUT_S16_MONO || fmt == (int)MP3G_OUT_F32_MONO; }
+constexpr bool fmt_is_mono(int fmt) {
+  return fmt == (int)MP3G_OUT_S16_MONO || fmt == (int)MP3G_OUT_F32_MONO || fmt == kFmtWinMono;
+}
+// the windowed formats (kernels.h): float planar / float mono samples placed
+// with sample granularity into dense rows
+constexpr bool fmt_is_windowed(int fmt) { return fmt == kFmtWinPlanar || fmt == kFmtWinMono; }
 #ifndef MP3G_MONO_S16_PACK
 #define MP3G_MONO_S16_PACK 0  // (A/B) s16 mono: pair neighbouring lanes' samples (one DPP move), dword stores from the even lanes
 #endif
@@ -1086,6 +1091,10 @@ template <>
 struct PcmRegs<(int)MP3G_OUT_F32_MONO> {
   typedef float type[9];
 };
+template <>
+struct PcmRegs<kFmtWinMono> {
+  typedef float type[9];
+};
 
 // Mono samples of granule g: sample 64 p + lane, non-temporal and issued for
 // replayed granules too (no records), nine stores per lane like the s16 path.
@@ -1115,6 +1124,99 @@ __device__ __forceinline__ void store_pcm_mono(int16_t* pcm, uint32_t g, bool ou
   for (int p = 0; p < 9; p++)
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pm[p]), rp, 4 * (64 * p + lane), 0,
                                           MP3G_PCM_STORE_AUX);
+}
+
+// ---- windowed output (kFmtWinPlanar / kFmtWinMono, kernels.h WindowRow) ----
+// The registers are those of the float planar / float mono formats; only the
+// placement differs: sample i of granule g goes to row index r = 576 (g - lo)
+// - skip + i when 0 <= r < n_valid.  The resource starts at the row (plane 0)
+// and spans it up to the last valid sample of its last plane; as many stores
+// as the other formats, replayed granules included (no records).  Every lane
+// is masked explicitly, by forcing its offset to kNoRecord:
+//   * the shift is negative in the window's first granule -- it is part of
+//     the VECTOR offset, never of the scalar offset operand, and a lane in
+//     front of the row is masked before its offset could wrap;
+//   * the range check alone cannot clip plane 0 at n_valid (the next bytes are
+//     plane 1's, or the next row's).
+// kNoRecord (2^30) lies past the records: 8 T <= 2^29 (MP3G_WINDOW_MAX_SAMPLES).
+// The mask is an add, a compare and a select per store.  A granule wholly
+// inside the window (a wave-uniform test) takes an unmasked path instead, the
+// slot as the instruction's immediate offset like the plain formats; both
+// paths issue the same number of stores.  The ISA and the measurement pull in
+// opposite directions here, and the measurement decides (DESIGN.md section
+// 9b): with two store sequences joining in front of the loop's back edge the
+// wait-count pass turns the back edge's s_waitcnt vmcnt(18) -- wait for the
+// prefetch, leave the 18 stores in flight, section 6 -- into vmcnt(0), yet
+// full-length windows run 2.1 % faster in the fast kernel and the 2-second
+// windows of c3 4.6 % faster than with every store masked
+// (-DMP3G_WIN_INSIDE_PATH=0: one straight line of masked stores, vmcnt(18)
+// kept): on this issue-bound kernel the 54 VALU instructions of the masks cost
+// more than the wait, which the SIMD's other waves cover.
+#ifndef MP3G_WIN_INSIDE_PATH
+#define MP3G_WIN_INSIDE_PATH 1
+#endif
+// The row of a chunk's stream as wave-uniform scalars, loaded once per chunk
+// -- in front of the granule loop and of the chunk's first store, so the
+// loads are settled with the prologue's (a load inside the loop would make the
+// store stage wait for the previous granule's stores).  off0 = 576 lo + skip
+// modulo 2^32: sample i of granule g has row index 576 g - off0 + i.
+struct WinGeom {
+  float* o;  // the row's first float (plane 0)
+  uint32_t off0, nv, plane;
+};
+__device__ __forceinline__ WinGeom win_geom(int16_t* pcm, const void* table, uint32_t stream) {
+  const WindowRow* row = static_cast<const WindowRow*>(table) + stream;
+  const uint64_t base = row->base;
+  const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)base);
+  const uint32_t bhi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
+  return WinGeom{reinterpret_cast<float*>(pcm) + (((uint64_t)bhi << 32) | blo),
+                 (uint32_t)__builtin_amdgcn_readfirstlane(576u * row->lo + row->skip),
+                 (uint32_t)__builtin_amdgcn_readfirstlane(row->n_valid),
+                 (uint32_t)__builtin_amdgcn_readfirstlane(row->plane)};
+}
+
+template <int kFmt>
+__device__ __forceinline__ void store_pcm_win(const WinGeom& wg, uint32_t g, bool out, const float* pf, int lane) {
+  const uint32_t nv = wg.nv;
+  const int shift = (int)(576u * g - wg.off0);
+  // (wave-uniform; constant false with -DMP3G_WIN_INSIDE_PATH=0)
+  const bool inside = MP3G_WIN_INSIDE_PATH && shift >= 0 && (uint32_t)shift + 576u <= nv;
+  if constexpr (kFmt == kFmtWinPlanar) {
+    const uint32_t plane = wg.plane;
+    const __amdgpu_buffer_rsrc_t rp =
+        __builtin_amdgcn_make_buffer_rsrc(wg.o, (short)0, out ? (int)(4u * (plane + nv)) : 0, 0x00020000);
+    const int r0 = shift + (lane & 31);
+    const int b4 = 4 * ((lane >> 5 ? (int)plane : 0) + r0);
+    if (inside) {
+#pragma unroll
+      for (int sl = 0; sl < 18; sl++)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[sl]), rp, b4 + 128 * sl, 0,
+                                              MP3G_PCM_STORE_AUX);
+    } else {
+#pragma unroll
+      for (int sl = 0; sl < 18; sl++)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[sl]), rp,
+                                              (uint32_t)(r0 + 32 * sl) < nv ? b4 + 128 * sl : kNoRecord, 0,
+                                              MP3G_PCM_STORE_AUX);
+    }
+  } else {
+    const __amdgpu_buffer_rsrc_t rp =
+        __builtin_amdgcn_make_buffer_rsrc(wg.o, (short)0, out ? (int)(4u * nv) : 0, 0x00020000);
+    const int r0 = shift + lane;
+    const int b4 = 4 * r0;
+    if (inside) {
+#pragma unroll
+      for (int p = 0; p < 9; p++)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[p]), rp, b4 + 256 * p, 0,
+                                              MP3G_PCM_STORE_AUX);
+    } else {
+#pragma unroll
+      for (int p = 0; p < 9; p++)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[p]), rp,
+                                              (uint32_t)(r0 + 64 * p) < nv ? b4 + 256 * p : kNoRecord, 0,
+                                              MP3G_PCM_STORE_AUX);
+    }
+  }
 }
 
 // Entry state of a replay start: overlap store in registers, V history as X
@@ -1338,6 +1440,10 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
   const uint32_t out_first = __builtin_amdgcn_readfirstlane((uint32_t)cd.out_first);
   const uint32_t end = __builtin_amdgcn_readfirstlane((uint32_t)(cd.out_first + cd.n_out));
   const mp3g_state* sin = state_in ? state_in + cd.stream : nullptr;
+  // (windowed output only: the stream's row; the table comes in place of
+  // state_out, kernels.h)
+  WinGeom wgeom = {nullptr, 0u, 0u, 0u};
+  if constexpr (fmt_is_windowed(kFmt)) wgeom = win_geom(pcm, state_out, cd.stream);
 
 
   // entry state: overlap store in registers, V history as X vectors
@@ -1445,7 +1551,21 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     geom = StreamGeom{(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)cd.stream_first),
                       (uint32_t)__builtin_amdgcn_readfirstlane(cd.stream_n)};
   auto window_store = [&](uint32_t g, bool out, int nch) {
-    if constexpr (fmt_is_mono(kFmt)) {
+    if constexpr (fmt_is_windowed(kFmt)) {
+      // the float planar / float mono registers, placed by store_pcm_win
+      typename PcmRegs<kFmt>::type pw;
+      if (out) {
+        f2 acc2[9];
+        window_acc(acc2);
+        if constexpr (fmt_is_mono(kFmt)) pack_pcm_mono(acc2, nch, pw);
+        else pack_pcm(acc2, nch, pw);
+      } else {
+#pragma unroll
+        for (int i = 0; i < (int)(sizeof(pw) / sizeof(pw[0])); i++) pw[i] = 0.0f;
+      }
+      store_pcm_win<kFmt>(wgeom, g, out, pw, lane_fresh());
+      return;
+    } else if constexpr (fmt_is_mono(kFmt)) {
       // one downmixed sample per lane and slot pair (replayed granules: zeros
       // to no records, the same number of stores)
       typename PcmRegs<kFmt>::type pm;

@@ -313,6 +313,10 @@ __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_gra
   if constexpr (kFmt == (int)MP3G_OUT_F32_PLANAR)
     geom = StreamGeom{(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)cd.stream_first),
                       (uint32_t)__builtin_amdgcn_readfirstlane(cd.stream_n)};
+  // (windowed output only: the stream's row; the table comes in place of
+  // state_out, kernels.h)
+  WinGeom wgeom = {nullptr, 0u, 0u, 0u};
+  if constexpr (fmt_is_windowed(kFmt)) wgeom = win_geom(pcm, state_out, cd.stream);
 
   uint32_t cw[9] = {};
   if (w < end) {
@@ -445,7 +449,8 @@ __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_gra
       if constexpr (fmt_is_mono(kFmt)) pack_pcm_mono(acc2, P.nch, pk);
       else pack_pcm(acc2, P.nch, pk);
     }
-    if constexpr (fmt_is_mono(kFmt)) store_pcm_mono(pcm, g, out, pk, lane_fresh());
+    if constexpr (fmt_is_windowed(kFmt)) store_pcm_win<kFmt>(wgeom, g, out, pk, lane_fresh());
+    else if constexpr (fmt_is_mono(kFmt)) store_pcm_mono(pcm, g, out, pk, lane_fresh());
     else if constexpr (kFmt == (int)MP3G_OUT_S16) store_pcm(pcm, g, out, pk, lane_fresh() >> 5, lane_fresh() & 31);
     else store_pcm_f32<kFmt>(pcm, geom, g, out, pk, lane_fresh() >> 5, lane_fresh() & 31);
     wave_sync();

@@ -654,6 +654,42 @@ void prescan(const uint8_t* data, size_t len, uint64_t* n_granules, uint64_t* md
   *md_bytes = nmd;
 }
 
+bool walk_frames(Source& src, uint64_t stop_granules, std::vector<WalkFrame>* frames, uint64_t* n_granules,
+                 Source::Mark* end_at) {
+  uint64_t ng = 0;
+  uint8_t skip[2048];
+  bool ended = false;
+  *end_at = src.mark();
+  while (ng < stop_granules) {  // prescan's checks, frame by frame
+    WalkFrame f;
+    f.at = src.mark();
+    *end_at = f.at;
+    uint32_t h;
+    int64_t pos = src.pos;
+    ended = true;
+    if (read_header(src, &pos, &h) != St::kOk) break;
+    f.offset = src.rpos - 4;  // (the unread bytes went first: the header's last byte came from the source)
+    const int crc = h_protection(h) == 0 ? 2 : 0;
+    if (h_id(h) == 0 || h_layer(h) != 1) break;
+    const int fsize = header_frame_size(h);
+    if (fsize < 0 || fsize > 2000) break;
+    const int sis = h_side_info_size(h);
+    const int size = fsize - sis - 4 - crc;
+    if (size > 1500 || size < 0) break;
+    bool sr;
+    if (src.read_full(skip, crc + sis + size, &sr) < crc + sis + size) break;
+    ended = false;
+    f.header = h;
+    f.md_bytes = (uint32_t)size;
+    f.first_granule = ng;
+    frames->push_back(f);
+    ng += (uint64_t)header_granules(h);
+    *end_at = src.mark();
+  }
+  *n_granules = ng;
+  return ended;
+}
+
 // ---- frame.Read (frame.go:67-115) + maindata.Read (maindata.go:85-117, :290-323) ----
 St FrameParser::next(Source& s, ParsedFrame* out) {
   std::call_once(g_lut_once, build_lut);

@@ -167,6 +167,22 @@ St read_header(Source& s, int64_t* pos_io, uint32_t* out);
 // that scans to EOF).
 void prescan(const uint8_t* data, size_t len, uint64_t* n_granules, uint64_t* md_bytes);
 
+// The same walk (prescan's checks, after skip_tags), keeping one record per
+// frame: where the scanner can be restarted at it, its header, main-data
+// bytes and first granule.  Stops once `stop_granules` granules are covered
+// (~0 = the stream's end); *end_at is the source state at the first frame not
+// walked (where FrameScanner::next yields the stream's end status when the
+// walk ended the stream).  Returns whether the walk reached the stream's end.
+struct WalkFrame {
+  Source::Mark at;     // source state in front of the frame's header
+  int64_t offset = 0;  // byte offset of the header in an in-memory source
+  uint32_t header = 0;
+  uint32_t md_bytes = 0;
+  uint64_t first_granule = 0;
+};
+bool walk_frames(Source& src, uint64_t stop_granules, std::vector<WalkFrame>* frames, uint64_t* n_granules,
+                 Source::Mark* end_at);
+
 // frameheader accessors used by the decoder
 int header_bytes_per_frame(uint32_t h);
 int header_frame_size(uint32_t h);

@@ -71,6 +71,8 @@ struct mp3g_scan {
   Buf<uint8_t> md;
   std::vector<mp3g_stream> streams;
   std::vector<int> status;
+  std::vector<mp3g_window_row> rows;  // mp3g_scan_windows: the per-stream layout
+  bool windowed = false;
 };
 
 namespace {
@@ -157,6 +159,150 @@ uint64_t scan_into(const uint8_t* data, size_t len, mp3g_granule* gran, mp3g_hjo
   return n;
 }
 
+// The stream's end status at `at`, the first frame a header walk did not
+// accept: what FrameScanner::next returns there (its checks do not depend on
+// the reservoir).
+St end_status_at(host::Source& src, const host::Source::Mark& at) {
+  src.restore(at);
+  host::FrameScanner sc;
+  host::ScannedFrame f;
+  uint8_t one[1];
+  host::RawMd md;
+  md.base = one;
+  const St st = sc.next(src, &f, &md);
+  return st == St::kOk ? St::kErr : st;
+}
+
+// One stream of mp3g_scan_windows (include/mp3g.h states the contract): the
+// frames of granules [h, hi) with the reservoir pre-roll in front of them.
+//
+// Pre-roll.  The reference's bit buffer of frame j is prev.Tail(main_data_begin)
+// ++ buf, prev being frame j - 1's BIT BUFFER (all of it on an underflow,
+// maindata.go:290-323), so a scanner restarted with an empty reservoir at frame
+// p sees, at every frame j >= p, a suffix of the full scan's buffer: by
+// induction its length is >= min(len_j, S_j), len_j the full scan's length and
+// S_j the main-data bytes of frames p .. j.  (Frame p: its own bytes.  Frame
+// j + 1 takes min(main_data_begin, previous length) bytes -- or all of a
+// previous buffer shorter than main_data_begin -- of a previous buffer that is
+// a suffix of the full scan's and at least min(len_j, S_j) long, then adds its
+// own.)  main_data_begin <= 511 (9 bits; 255 for LSF), so once the frames in
+// front of j hold S >= 511 bytes the restarted buffer is at least
+// min(len, 511) >= what frame j can reach back to: both scans take the same
+// tail, the buffers are equal, and stay equal.  p is therefore the latest
+// frame with >= 511 main-data bytes in frames p .. frame(h) - 1 (p = 0 if the
+// walk back reaches the first frame, where the restarted scan IS the full
+// scan): less than 511 bytes plus one frame's main data.
+void scan_window(const uint8_t* data, size_t len, const mp3g_window& w, StreamScan* out, mp3g_window_row* row) {
+  *row = mp3g_window_row{};
+  host::Source src;
+  src.data = data;
+  src.len = (int64_t)len;
+  St st = src.skip_tags();
+  if (st != St::kOk) {
+    out->end = st;
+    return;
+  }
+  const uint64_t T = w.n_samples;
+  uint64_t start = std::min<uint64_t>(w.start, 1ull << 62);
+  const bool gapless = (w.flags & MP3G_WINDOW_GAPLESS) != 0;
+  std::vector<host::WalkFrame> fr;
+  uint64_t W = 0;
+  host::Source::Mark end_at;
+  const bool ended = host::walk_frames(src, gapless ? ~0ull : (start + T + 575) / 576, &fr, &W, &end_at);
+  uint64_t avail_end = 576 * W;  // samples the window may take
+  if (gapless && !fr.empty()) {
+    const host::WalkFrame& f0 = fr[0];
+    const int fsize = host::header_frame_size(f0.header);
+    mp3g_lame_info info;
+    if (fsize >= 4 && f0.offset >= 0 && (uint64_t)f0.offset + (uint64_t)fsize <= len &&
+        mp3g_lame_parse(data + f0.offset, (size_t)fsize, &info) == MP3G_OK) {
+      uint64_t first = 0, count = 0;
+      (void)mp3g_lame_trim(&info, 576 * W, 576u * (uint32_t)host::header_granules(f0.header), &first, &count);
+      start = first + std::min(start, count);
+      avail_end = first + count;
+    }
+  }
+  // the end status of a window that wants more than the stream holds
+  auto finish_empty = [&]() {
+    out->gran.clear();
+    out->jobs.clear();
+    out->md.clear();
+    *row = mp3g_window_row{};
+  };
+  const bool past_end = ended && start + T > avail_end;
+  const uint64_t lo = start / 576, skip = start % 576;
+  uint64_t hi = std::min<uint64_t>((std::min(start + T, avail_end) + 575) / 576, W);
+  if (T == 0 || start >= avail_end || lo >= hi) {
+    out->end = past_end ? end_status_at(src, end_at) : St::kOk;
+    return;
+  }
+  auto frame_of = [&](uint64_t g) {  // the frame that holds granule g < W
+    size_t a = 0, b = fr.size();
+    while (b - a > 1) {
+      const size_t m = (a + b) / 2;
+      if (fr[m].first_granule <= g) a = m;
+      else b = m;
+    }
+    return a;
+  };
+  auto stereo = [](uint32_t h) { return ((h >> 6) & 3u) != 3u; };
+  // the replay start (the plans' rule, granule_fast.hip prologue): two
+  // granules back, and back to the second-latest stereo granule before lo (the
+  // only one when there is one) for channel 1's state across mono granules;
+  // no stereo granule before lo: channel 1's state is zero in either decode
+  uint64_t h = lo >= 2 ? lo - 2 : 0;
+  if (lo > 0) {
+    int found = 0;
+    uint64_t s_last = 0;
+    for (size_t fi = frame_of(lo - 1) + 1; fi-- > 0 && found < 2;) {
+      if (!stereo(fr[fi].header)) continue;
+      const uint64_t g0 = fr[fi].first_granule, g1 = std::min<uint64_t>(g0 + host::header_granules(fr[fi].header), lo);
+      for (uint64_t g = g1; g-- > g0 && found < 2;) {
+        found++;
+        s_last = g;
+      }
+    }
+    if (found) h = std::min(h, s_last);
+  }
+  const size_t fh = frame_of(h), fl = frame_of(hi - 1);
+  size_t p = fh;
+  for (uint64_t S = 0; p > 0 && S < 511;) S += fr[--p].md_bytes;
+  src.restore(fr[p].at);
+  host::FrameScanner sc;
+  host::ScannedFrame f;
+  uint64_t G = W;  // granules the scan accepts
+  st = St::kOk;
+  for (size_t fi = p; fi <= fl; fi++) {
+    st = sc.next(src, &f, &out->md);
+    if (st == St::kOk && f.header != fr[fi].header) st = St::kErr;  // (the walk and the scan read the same bytes)
+    if (st != St::kOk) {
+      G = fr[fi].first_granule;
+      break;
+    }
+    for (int gr = 0; gr < f.n_granules; gr++) {
+      const uint64_t g = fr[fi].first_granule + (uint64_t)gr;
+      if (g < h || g >= hi) continue;
+      out->gran.push_back(f.gran[gr]);
+      out->jobs.push_back(f.job[gr][0]);
+      out->jobs.push_back(f.job[gr][1]);
+    }
+  }
+  if (st != St::kOk) {  // a frame of the decoded range (or its pre-roll) ends the stream
+    out->end = st;
+    hi = std::min(hi, G);
+    avail_end = std::min(avail_end, 576 * G);
+    if (lo >= hi || start >= avail_end) {
+      finish_empty();
+      return;
+    }
+  } else {
+    out->end = past_end ? end_status_at(src, end_at) : St::kOk;
+  }
+  row->lead = (uint32_t)(lo - h);
+  row->skip = (uint32_t)skip;
+  row->n_valid = (uint32_t)std::min<uint64_t>(T, avail_end - start);
+}
+
 // fn(k) for k in [k0, k1) on up to nt threads (the calling thread included)
 template <class Fn>
 void parallel_for(uint32_t k0, uint32_t k1, int nt, Fn&& fn) {
@@ -169,6 +315,47 @@ void parallel_for(uint32_t k0, uint32_t k1, int nt, Fn&& fn) {
   for (int t = 1; t < nt; t++) pool.emplace_back(work);
   work();
   for (auto& t : pool) t.join();
+}
+
+// The per-stream scans concatenated into *s (the two-step path of
+// mp3g_scan_streams, and mp3g_scan_windows): job positions become absolute.
+bool merge_scans(std::vector<StreamScan>& per, int nt, mp3g_scan* s) {
+  const uint32_t n_streams = (uint32_t)per.size();
+  // where each stream lands; each stream's main data 16-B aligned, 16 zero
+  // bytes of padding after the last (the device reads whole 8-B words)
+  std::vector<uint64_t> g_at(n_streams + 1), m_at(n_streams + 1);
+  for (uint32_t k = 0; k < n_streams; k++) {
+    g_at[k + 1] = g_at[k] + per[k].gran.size();
+    m_at[k + 1] = m_at[k] + ((per[k].md.size() + 15) & ~(size_t)15);
+  }
+  const uint64_t ng = g_at[n_streams], nmd = m_at[n_streams];
+  if (!s->gran.alloc(ng) || !s->jobs.alloc(2 * ng) || !s->md.alloc(nmd + 16)) return false;
+  s->streams.resize(n_streams);
+  s->status.resize(n_streams);
+  std::memset(s->md.data() + nmd, 0, 16);
+  parallel_for(0, n_streams, nt, [&](uint32_t k) {
+    StreamScan& p = per[k];
+    const uint64_t g = g_at[k], m = m_at[k];
+    s->streams[k].first_granule = g;
+    s->streams[k].n_granules = (uint32_t)p.gran.size();
+    s->streams[k].flags = 0;
+    s->status[k] = to_status(p.end);
+    if (!p.gran.empty()) std::memcpy(&s->gran[g], p.gran.data(), p.gran.size() * sizeof(mp3g_granule));
+    for (size_t i = 0; i < p.jobs.size(); i++) {
+      mp3g_hjob J = p.jobs[i];
+      if (J.sf_kind != MP3G_SF_NONE) {
+        J.part2_start += 8 * m;
+        J.bit_end += 8 * m;
+      }
+      s->jobs[2 * g + i] = J;
+    }
+    if (!p.md.empty()) std::memcpy(&s->md[m], p.md.data(), p.md.size());
+    std::memset(&s->md[m + p.md.size()], 0, m_at[k + 1] - m - p.md.size());
+    std::vector<mp3g_granule>().swap(p.gran);  // release as we go
+    std::vector<mp3g_hjob>().swap(p.jobs);
+    std::vector<uint8_t>().swap(p.md);
+  });
+  return true;
 }
 
 // page-locked host memory and device memory that grow on demand
@@ -368,44 +555,40 @@ int mp3g_scan_streams(uint32_t n_streams, const uint8_t* const* datas, const siz
   }
   parallel([&](uint32_t k) { scan_all(datas[k], lens[k], &per[k]); });
 
-  // where each stream lands; each stream's main data 16-B aligned, 16 zero
-  // bytes of padding after the last (the device reads whole 8-B words)
-  std::vector<uint64_t> g_at(n_streams + 1), m_at(n_streams + 1);
-  for (uint32_t k = 0; k < n_streams; k++) {
-    g_at[k + 1] = g_at[k] + per[k].gran.size();
-    m_at[k + 1] = m_at[k] + ((per[k].md.size() + 15) & ~(size_t)15);
-  }
-  const uint64_t ng = g_at[n_streams], nmd = m_at[n_streams];
-  if (!s->gran.alloc(ng) || !s->jobs.alloc(2 * ng) || !s->md.alloc(nmd + 16)) {
+  if (!merge_scans(per, nt, s)) {
     delete s;
     return abi_fail(MP3G_ERR_OUT_OF_MEMORY, "scan buffers");
   }
-  s->streams.resize(n_streams);
-  s->status.resize(n_streams);
-  std::memset(s->md.data() + nmd, 0, 16);
-  parallel([&](uint32_t k) {
-    StreamScan& p = per[k];
-    const uint64_t g = g_at[k], m = m_at[k];
-    s->streams[k].first_granule = g;
-    s->streams[k].n_granules = (uint32_t)p.gran.size();
-    s->streams[k].flags = 0;
-    s->status[k] = to_status(p.end);
-    if (!p.gran.empty()) std::memcpy(&s->gran[g], p.gran.data(), p.gran.size() * sizeof(mp3g_granule));
-    for (size_t i = 0; i < p.jobs.size(); i++) {
-      mp3g_hjob J = p.jobs[i];
-      if (J.sf_kind != MP3G_SF_NONE) {
-        J.part2_start += 8 * m;
-        J.bit_end += 8 * m;
-      }
-      s->jobs[2 * g + i] = J;
-    }
-    if (!p.md.empty()) std::memcpy(&s->md[m], p.md.data(), p.md.size());
-    std::memset(&s->md[m + p.md.size()], 0, m_at[k + 1] - m - p.md.size());
-    std::vector<mp3g_granule>().swap(p.gran);  // release as we go
-    std::vector<mp3g_hjob>().swap(p.jobs);
-    std::vector<uint8_t>().swap(p.md);
-  });
   *out = s;
+  return MP3G_OK;
+}
+
+int mp3g_scan_windows(uint32_t n_streams, const uint8_t* const* datas, const size_t* lens,
+                      const mp3g_window* windows, int n_threads, mp3g_scan** out) {
+  if (!out || (n_streams && (!datas || !lens || !windows))) return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "null argument");
+  *out = nullptr;
+  for (uint32_t k = 0; k < n_streams; k++)
+    if (windows[k].n_samples > MP3G_WINDOW_MAX_SAMPLES || (windows[k].flags & ~(uint32_t)MP3G_WINDOW_GAPLESS))
+      return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "scan_windows: window");
+  mp3g_scan* s = new (std::nothrow) mp3g_scan;
+  if (!s) return abi_fail(MP3G_ERR_OUT_OF_MEMORY, "scan");
+  const int nt = std::max(1, std::min<int>(n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency(),
+                                           (int)std::max<uint32_t>(1, n_streams)));
+  std::vector<StreamScan> per(n_streams);
+  s->rows.resize(n_streams);
+  s->windowed = true;
+  parallel_for(0, n_streams, nt, [&](uint32_t k) { scan_window(datas[k], lens[k], windows[k], &per[k], &s->rows[k]); });
+  if (!merge_scans(per, nt, s)) {
+    delete s;
+    return abi_fail(MP3G_ERR_OUT_OF_MEMORY, "scan buffers");
+  }
+  *out = s;
+  return MP3G_OK;
+}
+
+int mp3g_scan_window_rows(const mp3g_scan* s, const mp3g_window_row** rows) {
+  if (!s || !rows || !s->windowed) return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "not a windowed scan");
+  *rows = s->rows.data();
   return MP3G_OK;
 }
 

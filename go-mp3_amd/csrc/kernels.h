@@ -27,6 +27,33 @@ struct ChunkDesc {
 };
 static_assert(sizeof(ChunkDesc) == 32, "ChunkDesc layout");
 
+// Windowed plans (mp3g_plan_create_windows): where the samples of a stream's
+// granules go.  A device table owned by the plan, indexed by
+// ChunkDesc::stream (the fast kernel's zone pieces copy `stream`, so the zone
+// launch finds the same entry).  Sample i of granule g lands at float
+// d_out[base + ch * plane + r], r = 576 (g - lo) - skip + i, if 0 <= r <
+// n_valid (32 bytes: one scalar load).
+struct WindowRow {
+  uint64_t base;     // the row's first float in d_out (plane 0)
+  uint32_t lo;       // the window's first granule (absolute index: first + lead)
+  uint32_t skip;     // samples of granule lo in front of the window (< 576)
+  uint32_t n_valid;  // samples written per plane (<= plane)
+  uint32_t plane;    // T: floats from plane 0 to plane 1 (planar rows)
+  uint32_t reserved[2];
+};
+static_assert(sizeof(WindowRow) == 32, "WindowRow layout");
+// The kernels' internal formats of a windowed launch (not MP3G_OUT_* values:
+// mp3g_out_bytes_per_granule is 0 for them, so no public call accepts them).
+// The launchers take the WindowRow table in place of d_state_out, which a
+// windowed plan never uses (no chunk of it exports state).
+constexpr int kFmtWinPlanar = 16;  // rows float [B][2][T]
+constexpr int kFmtWinMono = 17;    // rows float [B][T], (fL + fR) * 0.5f
+struct ZoneScratch;
+hipError_t launch_granule_windows(int variant, const ChunkDesc* d_chunks, uint32_t n_chunks,
+                                  const mp3g_granule* d_gran, const int16_t* d_coef, const WindowRow* d_rows,
+                                  void* d_out, int win_format, const ZoneScratch* zones, bool hot_stats,
+                                  hipStream_t stream);
+
 // Host-side launchers (defined next to the kernels; no RDC needed).
 hipError_t upload_tables(const DspTables& tables);
 // Exact-mode kernel variants: v2 = fused/register-blocked workgroup kernel

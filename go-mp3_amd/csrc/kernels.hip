@@ -143,4 +143,21 @@ hipError_t launch_granule(int variant, const ChunkDesc* d_chunks, uint32_t n_chu
   return hipGetLastError();
 }
 
+// A windowed plan's launch (kernels.h): the one-wave kernels' windowed
+// instantiations, the row table travelling in the state_out argument.
+hipError_t launch_granule_windows(int variant, const ChunkDesc* d_chunks, uint32_t n_chunks,
+                                  const mp3g_granule* d_gran, const int16_t* d_coef, const WindowRow* d_rows,
+                                  void* d_out, int win_format, const ZoneScratch* zones, bool hot_stats,
+                                  hipStream_t stream) {
+  if (n_chunks == 0) return hipSuccess;
+  if ((win_format != kFmtWinPlanar && win_format != kFmtWinMono) || !d_rows) return hipErrorInvalidValue;
+  mp3g_state* const rows_arg = reinterpret_cast<mp3g_state*>(const_cast<WindowRow*>(d_rows));
+  if (variant == kVariantFast)
+    return launch_fast(d_chunks, n_chunks, d_gran, d_coef, nullptr, rows_arg, d_out, (uint32_t)win_format, nullptr,
+                       zones, hot_stats, stream);
+  if (variant == kVariantExact4)
+    return launch_wexact(d_chunks, n_chunks, d_gran, d_coef, nullptr, rows_arg, d_out, (uint32_t)win_format, stream);
+  return hipErrorInvalidValue;
+}
+
 }  // namespace mp3g

@@ -139,6 +139,13 @@ hipError_t launch_fast(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_
     case MP3G_OUT_F32_MONO:
       return launch_fast_fmt<MP3G_OUT_F32_MONO>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
                                                 zones, hot_stats, stream);
+    // windowed plans (launch_granule_windows: the WindowRow table in d_state_out)
+    case kFmtWinPlanar:
+      return launch_fast_fmt<kFmtWinPlanar>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, zones,
+                                            hot_stats, stream);
+    case kFmtWinMono:
+      return launch_fast_fmt<kFmtWinMono>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, zones,
+                                          hot_stats, stream);
   }
   return hipErrorInvalidValue;
 }
@@ -167,6 +174,11 @@ hipError_t launch_wexact(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3
     case MP3G_OUT_F32_MONO:
       return launch_wexact_fmt<MP3G_OUT_F32_MONO>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
                                                   stream);
+    case kFmtWinPlanar:
+      return launch_wexact_fmt<kFmtWinPlanar>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
+                                              stream);
+    case kFmtWinMono:
+      return launch_wexact_fmt<kFmtWinMono>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, stream);
   }
   return hipErrorInvalidValue;
 }

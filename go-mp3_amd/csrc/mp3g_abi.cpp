@@ -309,6 +309,12 @@ struct mp3g_plan {
   uint32_t zone_cap = 0;
   uint64_t n_granules = 0;
   uint64_t n_halo = 0;
+  // windowed plans (mp3g_plan_create_windows): the row tables of the two
+  // output layouts, behind the chunk table in the same allocation
+  bool windowed = false;
+  uint32_t win_T = 0;
+  WindowRow* d_rows_planar = nullptr;  // rows float [B][2][T]
+  WindowRow* d_rows_mono = nullptr;    // rows float [B][T]
 };
 
 extern "C" {
@@ -474,6 +480,7 @@ int mp3g_plan_execute_out(mp3g_plan* p, const mp3g_granule* d_gran, const int16_
                           uint32_t out_format, void* hip_stream) {
   if (!mp3g_out_bytes_per_granule(out_format)) return fail(MP3G_ERR_INVALID_ARGUMENT, "unknown output format");
   if (!p) return fail(MP3G_ERR_INVALID_ARGUMENT, "null plan");
+  if (p->windowed) return fail(MP3G_ERR_INVALID_ARGUMENT, "a windowed plan runs with mp3g_plan_execute_windows");
   if (out_format != MP3G_OUT_S16 && plan_variant(p->mode) == kVariantV2)
     return fail(MP3G_ERR_UNSUPPORTED, "this output format needs the one-wave kernels (no MP3G_FLAG_KERNEL_V2)");
   if (out_format == MP3G_OUT_F32_PLANAR) {
@@ -492,6 +499,115 @@ int mp3g_plan_execute_out(mp3g_plan* p, const mp3g_granule* d_gran, const int16_
   const ZoneScratch zs{static_cast<uint32_t*>(p->d_zones), p->zone_cap};
   return plan_launch_out(p->mode, p->d_chunks, (uint32_t)p->chunks.size(), d_gran, d_coef, d_state_in, d_state_out,
                          d_pcm, out_format, p->d_zones ? &zs : nullptr, static_cast<hipStream_t>(hip_stream));
+}
+
+// Windowed plans (include/mp3g.h).  The chunk table is that of the streams
+// [first + lead, first + n) -- so the cost model runs on the windowed lengths
+// -- with stream_first moved back to `first`: the first chunk of a windowed
+// stream is then a chunk that does not start its stream, and the kernels'
+// prologue replays the lead from zero state with PCM off.
+int mp3g_plan_create_windows(int device, const mp3g_stream* streams, const mp3g_window_row* rows,
+                             uint32_t n_streams, uint32_t T, uint32_t granules_per_chunk, uint32_t mode,
+                             mp3g_plan** out_plan) {
+  if (!out_plan) return fail(MP3G_ERR_INVALID_ARGUMENT, "null argument");
+  *out_plan = nullptr;
+  if (n_streams && (!streams || !rows)) return fail(MP3G_ERR_INVALID_ARGUMENT, "null argument");
+  if (mode & MP3G_FLAG_KERNEL_V2)
+    return fail(MP3G_ERR_UNSUPPORTED, "windowed plans need the one-wave kernels (no MP3G_FLAG_KERNEL_V2)");
+  if (T == 0 || T > MP3G_WINDOW_MAX_SAMPLES) return fail(MP3G_ERR_INVALID_ARGUMENT, "windowed plan: row length");
+  std::vector<mp3g_stream> cut(n_streams);
+  for (uint32_t s = 0; s < n_streams; s++) {
+    const mp3g_stream& S = streams[s];
+    const mp3g_window_row& R = rows[s];
+    // every sample the kernels may write lies inside the row: n_valid <= T,
+    // and the decoded granules behind the lead hold the window
+    if (S.flags || R.lead > S.n_granules || R.skip >= MP3G_LINES || R.n_valid > T ||
+        (uint64_t)(S.n_granules - R.lead) * MP3G_LINES < (uint64_t)R.skip + R.n_valid)
+      return fail(MP3G_ERR_INVALID_ARGUMENT, "windowed plan: row layout");
+    if (S.n_granules >= MP3G_PLANAR_MAX_GRANULES)  // (the lanes' sample shift is a 31-bit byte offset)
+      return fail(MP3G_ERR_UNSUPPORTED, "windowed plan: run of MP3G_PLANAR_MAX_GRANULES granules or more");
+    cut[s] = mp3g_stream{S.first_granule + R.lead, S.n_granules - R.lead, 0u};
+  }
+  mp3g_plan* p = new (std::nothrow) mp3g_plan;
+  if (!p) return fail(MP3G_ERR_OUT_OF_MEMORY, "plan");
+  int st = mp3g::plan_chunks(device, cut.data(), n_streams, granules_per_chunk, mode, &p->chunks, &p->n_granules,
+                             &p->n_halo);
+  if (st) {
+    delete p;
+    return st;
+  }
+  for (ChunkDesc& c : p->chunks) c.stream_first = streams[c.stream].first_granule;
+  std::vector<WindowRow> tab(2 * (size_t)n_streams);
+  for (uint32_t s = 0; s < n_streams; s++) {
+    if (streams[s].n_granules > rows[s].lead) p->n_halo += rows[s].lead;
+    WindowRow r{};
+    r.lo = (uint32_t)(streams[s].first_granule + rows[s].lead);
+    r.skip = rows[s].skip;
+    r.n_valid = rows[s].n_valid;
+    r.plane = T;
+    r.base = (uint64_t)s * 2u * T;
+    tab[s] = r;
+    r.base = (uint64_t)s * T;
+    tab[n_streams + s] = r;
+  }
+  p->device = device;
+  p->mode = mode;
+  p->n_streams = n_streams;
+  p->windowed = true;
+  p->win_T = T;
+  DeviceGuard guard(device);
+  // the chunk table, the two row tables, then the zone scratch (as mp3g_plan_create)
+  const size_t tb = (p->chunks.size() * sizeof(ChunkDesc) + 255) & ~(size_t)255;
+  const size_t rb = (tab.size() * sizeof(WindowRow) + 255) & ~(size_t)255;
+  const bool fast = plan_variant(mode) == kVariantFast;
+  const uint64_t zone_cap = fast ? zone_list_capacity(p->chunks.data(), p->chunks.size()) : 0u;
+  if (zone_cap > 0xffffffffu) {
+    delete p;
+    return fail(MP3G_ERR_UNSUPPORTED, "fast-mode plan of more than 2^29 chunks");
+  }
+  p->zone_cap = (uint32_t)zone_cap;
+  const size_t zb = fast ? zone_scratch_bytes(p->zone_cap) : 0;
+  hipError_t e = hipMalloc(&p->d_chunks, std::max<size_t>(tb + rb + zb, 256));
+  if (e != hipSuccess) {
+    delete p;
+    return fail(MP3G_ERR_OUT_OF_MEMORY, "hipMalloc(chunks)", e);
+  }
+  uint8_t* const b0 = reinterpret_cast<uint8_t*>(p->d_chunks);
+  p->d_rows_planar = reinterpret_cast<WindowRow*>(b0 + tb);
+  p->d_rows_mono = p->d_rows_planar + n_streams;
+  if (fast) p->d_zones = b0 + tb + rb;
+  if (!p->chunks.empty())
+    e = hipMemcpy(p->d_chunks, p->chunks.data(), p->chunks.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !tab.empty())
+    e = hipMemcpy(p->d_rows_planar, tab.data(), tab.size() * sizeof(WindowRow), hipMemcpyHostToDevice);
+  if (e == hipSuccess && fast) e = zone_scratch_init(p->d_zones, p->zone_cap);
+  if (e != hipSuccess) {
+    (void)hipFree(p->d_chunks);
+    delete p;
+    return fail(MP3G_ERR_DEVICE, "hipMemcpy(chunks)", e);
+  }
+  *out_plan = p;
+  return MP3G_OK;
+}
+
+int mp3g_plan_execute_windows(mp3g_plan* p, const mp3g_granule* d_gran, const int16_t* d_coef, void* d_out,
+                              uint32_t out_format, void* hip_stream) {
+  if (!mp3g_out_bytes_per_granule(out_format)) return fail(MP3G_ERR_INVALID_ARGUMENT, "unknown output format");
+  if (out_format != MP3G_OUT_F32_PLANAR && out_format != MP3G_OUT_F32_MONO)
+    return fail(MP3G_ERR_UNSUPPORTED, "windowed output is MP3G_OUT_F32_PLANAR or MP3G_OUT_F32_MONO");
+  if (!p) return fail(MP3G_ERR_INVALID_ARGUMENT, "null plan");
+  if (!p->windowed) return fail(MP3G_ERR_INVALID_ARGUMENT, "not a windowed plan");
+  if (p->chunks.empty()) return MP3G_OK;
+  if (!d_gran || !d_coef || !d_out) return fail(MP3G_ERR_INVALID_ARGUMENT, "null device buffer");
+  DeviceGuard guard(p->device);
+  if (guard.err != hipSuccess) return fail(MP3G_ERR_NO_DEVICE, "hipSetDevice", guard.err);
+  const ZoneScratch zs{static_cast<uint32_t*>(p->d_zones), p->zone_cap};
+  const bool planar = out_format == MP3G_OUT_F32_PLANAR;
+  HIP_TRY(launch_granule_windows(plan_variant(p->mode), p->d_chunks, (uint32_t)p->chunks.size(), d_gran, d_coef,
+                                 planar ? p->d_rows_planar : p->d_rows_mono, d_out,
+                                 planar ? kFmtWinPlanar : kFmtWinMono, p->d_zones ? &zs : nullptr,
+                                 (p->mode & MP3G_FLAG_HOT_STATS) != 0, static_cast<hipStream_t>(hip_stream)));
+  return MP3G_OK;
 }
 
 // The fast kernel's hot-granule counters of this plan (MP3G_FLAG_HOT_STATS),
@@ -516,6 +632,7 @@ int mp3g_plan_synth_execute(mp3g_plan* p, const mp3g_granule* d_gran, const floa
                             const mp3g_state* d_state_in, mp3g_state* d_state_out, int16_t* d_pcm, void* hip_stream) {
   if (!p) return fail(MP3G_ERR_INVALID_ARGUMENT, "null plan");
   if ((p->mode & 0xffu) != MP3G_MODE_FAST) return fail(MP3G_ERR_INVALID_ARGUMENT, "not a fast-mode plan");
+  if (p->windowed) return fail(MP3G_ERR_INVALID_ARGUMENT, "a windowed plan runs with mp3g_plan_execute_windows");
   if (p->chunks.empty()) return MP3G_OK;
   if (!d_gran || !d_lines || !d_pcm) return fail(MP3G_ERR_INVALID_ARGUMENT, "null device buffer");
   DeviceGuard guard(p->device);
@@ -587,6 +704,7 @@ uint32_t mp3g_huffman_stage_flags(const mp3g_hjob* jobs, uint64_t n_granules) {
 static int run_stamped(mp3g_plan* p, const mp3g_granule* d_gran, const int16_t* d_coef, int16_t* d_pcm,
                        std::vector<unsigned long long>* h, void* hip_stream) {
   if ((p->mode & 0xffu) != MP3G_MODE_FAST) return fail(MP3G_ERR_INVALID_ARGUMENT, "not a fast-mode plan");
+  if (p->windowed) return fail(MP3G_ERR_INVALID_ARGUMENT, "a windowed plan runs with mp3g_plan_execute_windows");
   for (const ChunkDesc& c : p->chunks)
     if (c.flags & (kChunkStateIn | kChunkStateOut)) return fail(MP3G_ERR_INVALID_ARGUMENT, "stateful plan");
   h->assign(p->chunks.size() * kFastStampSlots, 0ull);

@@ -17,7 +17,9 @@ __all__ = ["CHANNEL_DTYPE", "GRANULE_DTYPE", "STREAM_DTYPE", "STATE_DTYPE", "MOD
            "MODE_FAST", "FLAG_CHECKED", "FLAG_KERNEL_V1", "FLAG_KERNEL_V2", "FLAG_HOT_STATS", "FLAG_HOST_HUFFMAN", "STATE_IN", "STATE_OUT", "Mp3gError", "lib", "lib_path",
            "decode_host", "validate", "Plan", "device_count", "streams_for", "parse_stream",
            "parse_streams", "Decoder", "HJOB_DTYPE", "scan_streams", "huffman_execute", "HUFF_ROWS_COUNT1",
-           "HUFF_STAGE_WIDE", "HUFF_STAGE_MID", "huffman_stage_flags", "decode_streams"]
+           "HUFF_STAGE_WIDE", "HUFF_STAGE_MID", "huffman_stage_flags", "decode_streams",
+           "WINDOW_DTYPE", "WINDOW_ROW_DTYPE", "WINDOW_GAPLESS", "scan_windows", "WindowPlan",
+           "decode_windows_tensor"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -36,6 +38,11 @@ HJOB_DTYPE = np.dtype([("part2_start", "<u8"), ("bit_end", "<u8"), ("scf0_delta"
                        ("region2_start", "<u2"), ("table_select", "u1", (3,)), ("count1_table", "u1"),
                        ("sf_kind", "u1"), ("scfsi", "u1"), ("slen", "u1", (4,)), ("nsf", "u1", (4,)),
                        ("sf0_kind", "u1"), ("sf0_slen", "u1", (2,)), ("reserved", "u1", (3,))])
+# sample windows (mp3g_window) and the layout a windowed scan returns (mp3g_window_row)
+WINDOW_DTYPE = np.dtype([("start", "<u8"), ("n_samples", "<u4"), ("flags", "<u4")])
+WINDOW_ROW_DTYPE = np.dtype([("lead", "<u4"), ("skip", "<u4"), ("n_valid", "<u4"), ("reserved", "<u4")])
+WINDOW_GAPLESS = 1
+assert WINDOW_DTYPE.itemsize == 16 and WINDOW_ROW_DTYPE.itemsize == 16
 assert CHANNEL_DTYPE.itemsize == 72 and GRANULE_DTYPE.itemsize == 160 and HJOB_DTYPE.itemsize == 48
 assert STREAM_DTYPE.itemsize == 16 and STATE_DTYPE.itemsize == 12800
 
@@ -122,6 +129,11 @@ def lib():
         L.mp3g_scan_streams.argtypes = [u32, vp, vp, C.c_int, C.POINTER(vp)]
         L.mp3g_scan_buffers.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)] + [C.POINTER(vp)] * 5
         L.mp3g_scan_free.argtypes = [vp]
+        if hasattr(L, "mp3g_scan_windows"):  # (an older build through MP3G_LIB: A/B runs)
+            L.mp3g_scan_windows.argtypes = [u32, vp, vp, vp, C.c_int, C.POINTER(vp)]
+            L.mp3g_scan_window_rows.argtypes = [vp, C.POINTER(vp)]
+            L.mp3g_plan_create_windows.argtypes = [C.c_int, vp, vp, u32, u32, u32, u32, C.POINTER(vp)]
+            L.mp3g_plan_execute_windows.argtypes = [vp, vp, vp, vp, u32, vp]
         L.mp3g_lame_parse.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo)]
         L.mp3g_lame_parse_reader.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo), C.POINTER(C.c_size_t)]
         L.mp3g_lame_total_delay.argtypes = [C.POINTER(_LameInfo)]
@@ -470,7 +482,9 @@ def decode_streams_tensor(datas, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, n_t
     576) on cuda:device; views[k] is stream k's part of it, a slice --
     [2, T] for OUT_F32_PLANAR, [T, 2] for the interleaved formats, [T] for
     the mono formats, T = 576 * n_granules.  streams / end_status as
-    decode_streams.  No gapless trimming: slice a view with LameInfo.trim."""
+    decode_streams.  Whole streams, untrimmed: decode_windows_tensor decodes
+    a crop of each stream (gapless=True: counted from the first sample
+    LameInfo.trim keeps) straight into a dense batch."""
     import torch
     if not out_bytes_per_granule(out_format):
         raise Mp3gError(1, "unknown output format")
@@ -503,6 +517,78 @@ def decode_streams_tensor(datas, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, n_t
         views = [out[int(f) * 1152:(int(f) + int(k)) * 1152].reshape(int(k) * 576, 2)
                  for f, k in zip(streams["first_granule"], streams["n_granules"])]
     return out, views, streams, s["end_status"]
+
+
+def scan_windows(datas, starts, n_samples, gapless=False, n_threads=0):
+    """Windowed host scan (mp3g_scan_windows): only the frames the window
+    (starts[k], n_samples) of each stream needs.  Returns scan_streams' dict
+    (the stream table describes each stream's decoded run) plus "rows"
+    [WINDOW_ROW_DTYPE]: lead (granules decoded with PCM off), skip (samples of
+    the window's first granule in front of it) and n_valid (samples the row
+    receives).  gapless: a bool, or one per stream."""
+    bufs, ptrs, lens = _stream_args(datas)
+    win = np.zeros(max(1, len(datas)), WINDOW_DTYPE)
+    win["start"][:len(datas)] = np.asarray(starts, dtype=np.uint64)
+    win["n_samples"] = int(n_samples)
+    win["flags"][:len(datas)] = np.where(np.broadcast_to(np.asarray(gapless, dtype=bool), (len(datas),)),
+                                         WINDOW_GAPLESS, 0)
+    h = C.c_void_p()
+    t0 = time.perf_counter()
+    _check(lib().mp3g_scan_windows(len(datas), ptrs, lens, _ptr(win), n_threads, C.byref(h)))
+    scan_s = time.perf_counter() - t0
+    try:
+        ng, nmd = C.c_uint64(), C.c_uint64()
+        pg, pj, pm, ps, pst, pr = (C.c_void_p() for _ in range(6))
+        _check(lib().mp3g_scan_buffers(h, C.byref(ng), C.byref(nmd), C.byref(pg), C.byref(pj), C.byref(pm),
+                                       C.byref(ps), C.byref(pst)))
+        _check(lib().mp3g_scan_window_rows(h, C.byref(pr)))
+        n = ng.value
+        return {"granules": _copy_out(pg, n * GRANULE_DTYPE.itemsize, GRANULE_DTYPE),
+                "jobs": _copy_out(pj, 2 * n * HJOB_DTYPE.itemsize, HJOB_DTYPE),
+                "main_data": _copy_out(pm, nmd.value, np.uint8),
+                "streams": _copy_out(ps, len(datas) * STREAM_DTYPE.itemsize, STREAM_DTYPE),
+                "end_status": _copy_out(pst, len(datas) * 4, np.int32),
+                "rows": _copy_out(pr, len(datas) * WINDOW_ROW_DTYPE.itemsize, WINDOW_ROW_DTYPE),
+                "scan_s": scan_s}
+    finally:
+        lib().mp3g_scan_free(h)
+
+
+def decode_windows_tensor(datas, starts, n_samples, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, gapless=False,
+                          n_threads=0, device=0):
+    """A crop of every stream, decoded straight into one dense batch tensor:
+    row k holds samples [starts[k], starts[k] + lengths[k]) of stream k's full
+    decode (gapless=True: counted from the first sample LameInfo.trim keeps,
+    and capped by its count), zero-padded to n_samples.  Only the frames each
+    window needs are scanned and decoded (scan_windows, WindowPlan); the
+    samples are bit-identical to the same slice of decode_streams_tensor in
+    the same mode and format.
+
+    Returns (batch, lengths, end_status): batch a torch.zeros tensor
+    [B, 2, n_samples] (OUT_F32_PLANAR) or [B, n_samples] (OUT_F32_MONO) on
+    cuda:device, lengths int64[B], end_status as scan_windows (0 when the
+    window was filled before the stream's end).  Runs on the current torch
+    stream and returns when the kernels are done."""
+    import torch
+    if out_format not in (OUT_F32_PLANAR, OUT_F32_MONO):
+        raise Mp3gError(8 if out_bytes_per_granule(out_format) else 1, "windowed output is OUT_F32_PLANAR or OUT_F32_MONO")
+    s = scan_windows(datas, starts, n_samples, gapless=gapless, n_threads=n_threads)
+    n, B, T = len(s["granules"]), len(datas), int(n_samples)
+    dev = torch.device("cuda", device)
+    batch = torch.zeros((B, 2, T) if out_format == OUT_F32_PLANAR else (B, T), dtype=torch.float32, device=dev)
+    if n:
+        d_g = torch.from_numpy(s["granules"].view(np.uint8)).to(dev)
+        d_j = torch.from_numpy(s["jobs"].view(np.uint8)).to(dev)
+        d_m = torch.from_numpy(s["main_data"]).to(dev)
+        d_c = torch.empty(n * 1152, dtype=torch.int16, device=dev)
+        plan = WindowPlan(s["streams"], s["rows"], T, mode=mode, device=device)
+        st = torch.cuda.current_stream(dev)
+        flags = HUFF_ROWS_COUNT1 | huffman_stage_flags(s["jobs"], n)
+        huffman_execute(d_j, n, d_m, d_g, d_c, stream=st.cuda_stream, device=device, flags=flags)
+        plan.execute(d_g, d_c, batch, stream=st.cuda_stream, out_format=out_format)
+        st.synchronize()
+        plan.close()
+    return batch, s["rows"]["n_valid"].astype(np.int64), s["end_status"]
 
 
 def _host_buffer(out, want_int16, want_float32=False):
@@ -780,3 +866,27 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+class WindowPlan(Plan):
+    """Plan over windowed runs (mp3g_plan_create_windows): streams / rows as
+    scan_windows returns them, T the row length in samples."""
+
+    def __init__(self, streams, rows, T, granules_per_chunk=0, mode=MODE_EXACT, device=0):
+        streams = np.ascontiguousarray(streams, dtype=STREAM_DTYPE)
+        rows = np.ascontiguousarray(rows, dtype=WINDOW_ROW_DTYPE)
+        if len(rows) != len(streams):
+            raise ValueError("WindowPlan: one row per stream")
+        self._h = C.c_void_p()
+        self.device = device
+        _check(lib().mp3g_plan_create_windows(device, _ptr(streams), _ptr(rows), len(streams), int(T),
+                                              granules_per_chunk, mode, C.byref(self._h)))
+
+    def execute(self, d_gran, d_coef, d_out, stream=None, out_format=OUT_F32_PLANAR):
+        """d_out: float32 [B, 2, T] (OUT_F32_PLANAR) or [B, T] (OUT_F32_MONO) on
+        the device; only the rows' n_valid samples are written
+        (mp3g_plan_execute_windows)."""
+        def p(x):
+            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        _check(lib().mp3g_plan_execute_windows(self._h, p(d_gran), p(d_coef), p(d_out), int(out_format),
+                                               C.c_void_p(stream) if stream else None))

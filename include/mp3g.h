@@ -49,7 +49,9 @@ extern "C" {
  *    float32 PCM output -- MP3G_OUT_*, mp3g_out_bytes_per_granule,
  *    mp3g_plan_execute_out and mp3g_decode_host_out; the mono downmix
  *    formats MP3G_OUT_S16_MONO / MP3G_OUT_F32_MONO and
- *    mp3g_decode_streams_into_out.) */
+ *    mp3g_decode_streams_into_out; sample-windowed decode into dense rows --
+ *    mp3g_scan_windows, mp3g_scan_window_rows, mp3g_plan_create_windows and
+ *    mp3g_plan_execute_windows.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -447,6 +449,97 @@ int mp3g_decode_streams_into_out(int device, uint32_t n_streams, const uint8_t* 
 /* mp3g_decode_streams_into keeps its staging (page-locked) and device
  * buffers per device between calls; this frees them (idle sets only). */
 void mp3g_release_cached_buffers(void);
+
+/* ---- sample-windowed decode into dense rows -------------------------------
+ * A batch of B clips of T samples, one per stream, without decoding the files
+ * around them.  For stream k a window is (start, n_samples): `start` is a
+ * per-channel sample index into the stream's full decode (the sequence
+ * mp3g_scan_streams + mp3g_plan_execute_out produce, untrimmed); row k of the
+ * output receives samples [start, start + n_valid), n_valid = min(n_samples,
+ * available - start) clamped at 0, and the plan writes only those samples:
+ * the rest of the rows is the caller's (zero it first for a padded batch).
+ *   MP3G_OUT_F32_PLANAR  float [B][2][T]  (channel stride T, row stride 2 T;
+ *                        mono granules write channel 0 to both planes)
+ *   MP3G_OUT_F32_MONO    float [B][T]
+ * Every written float is bit-identical to the same sample of the full decode
+ * of the stream in the same format and mode (fast mode: to the fast-mode full
+ * decode, hot zones included).
+ *
+ * Host scan.  Only the frames a window needs are scanned: granules [h, hi) of
+ * the stream, lo = start / 576, hi = ceil((start + n_samples) / 576) capped at
+ * the stream's granules, and h <= lo the plans' replay start ("halo": two
+ * granules back, further back to the second-latest stereo granule before lo
+ * -- the only one when there is one -- so that channel 1's state is right
+ * across mono granules; lo - 2 when no stereo granule precedes lo, where
+ * channel 1's state is zero in either decode).  Granules [h, lo) are decoded
+ * with PCM off.  The scanner restarts with an empty bit reservoir at a frame p
+ * <= frame(h), chosen so that frames p .. frame(h) - 1 hold at least 511 bytes
+ * of main data (p = 0 when the walk back reaches the first frame): their main
+ * data is appended, no jobs are emitted for them, and from frame(h) on every
+ * bit buffer equals the full scan's (main_data_begin <= 511).  A stream's
+ * main data in the scan is therefore its window frames' own plus less than 511
+ * bytes and one frame's (<= 1,500 bytes): the file is not copied.
+ *
+ * Difference from the full decode: frames in front of frame p are only
+ * header-walked, with the checks of the header-only pre-pass (sync search,
+ * version, layer, frame and main-data sizes) -- as the reference's Seek trusts
+ * the header walk of ensureFrameStartsAndLength (decode.go:154-216).  A side
+ * info-level error in such a frame (which ends the full decode there) is not
+ * seen.  From frame p on a frame the reference rejects ends the stream at
+ * that frame with the end_status of the full scan; n_valid then counts the
+ * samples before that frame.  end_status is MP3G_OK when the window was
+ * filled before the stream's end was reached.
+ *
+ * MP3G_WINDOW_GAPLESS: the header walk goes to the stream's end, the first
+ * frame's Xing / Info / LAME tag is read, `start` counts from the first kept
+ * sample of mp3g_lame_trim and n_valid is capped by its count.  A stream
+ * without a tag behaves as if the flag were off. */
+#define MP3G_WINDOW_GAPLESS 1u
+#define MP3G_WINDOW_MAX_SAMPLES (1u << 26) /* n_samples and T (rows are addressed with 30-bit byte offsets) */
+typedef struct mp3g_window {
+  uint64_t start;     /* first sample, per channel */
+  uint32_t n_samples; /* samples wanted (<= the T of the plan) */
+  uint32_t flags;     /* MP3G_WINDOW_* */
+} mp3g_window;
+/* Where stream k's window lies in its decoded run (the scan's stream table
+ * describes that run, granules [h, hi)): `lead` = lo - h granules decoded with
+ * PCM off, `skip` = start mod 576 samples of granule lo in front of the
+ * window, n_valid samples written.  A window past the stream's end has an
+ * empty run and an all-zero row. */
+typedef struct mp3g_window_row {
+  uint32_t lead;
+  uint32_t skip;
+  uint32_t n_valid;
+  uint32_t reserved;
+} mp3g_window_row;
+/* Returns an ordinary mp3g_scan (mp3g_scan_buffers / mp3g_scan_free). */
+int mp3g_scan_windows(uint32_t n_streams, const uint8_t* const* datas, const size_t* lens,
+                      const mp3g_window* windows, int n_threads, mp3g_scan** out);
+/* The per-stream layout of a windowed scan ([n_streams], owned by the scan);
+ * MP3G_ERR_INVALID_ARGUMENT for a scan mp3g_scan_streams made. */
+int mp3g_scan_window_rows(const mp3g_scan* scan, const mp3g_window_row** rows);
+
+/* A plan over windowed runs: streams / rows as the windowed scan returns them
+ * (n of each), T = the row length in samples (every n_valid <= T <=
+ * MP3G_WINDOW_MAX_SAMPLES).  Chunks cover only granules [first + lead, first
+ * + n) of each stream -- its first chunk replays the lead as any chunk that
+ * does not start its stream replays its halo -- and the automatic chunk
+ * length is modelled on those lengths; mp3g_plan_info counts the lead in
+ * n_halo_granules.  mode: MP3G_MODE_EXACT or MP3G_MODE_FAST (|
+ * MP3G_FLAG_HOT_STATS); MP3G_FLAG_KERNEL_V2 is MP3G_ERR_UNSUPPORTED (checked
+ * before any device call).  Such a plan runs with mp3g_plan_execute_windows
+ * only. */
+int mp3g_plan_create_windows(int device, const mp3g_stream* streams, const mp3g_window_row* rows,
+                             uint32_t n_streams, uint32_t T, uint32_t granules_per_chunk, uint32_t mode,
+                             mp3g_plan** out_plan);
+/* d_out: float [n_streams][2][T] (MP3G_OUT_F32_PLANAR) or [n_streams][T]
+ * (MP3G_OUT_F32_MONO); only the n_valid samples of each row (and plane) are
+ * written.  An unknown format is MP3G_ERR_INVALID_ARGUMENT, the other known
+ * formats MP3G_ERR_UNSUPPORTED, both before any device call.  Asynchronous on
+ * hip_stream; executions of one plan must be stream-ordered (as
+ * mp3g_plan_execute). */
+int mp3g_plan_execute_windows(mp3g_plan* plan, const mp3g_granule* d_granules, const int16_t* d_coeffs,
+                              void* d_out, uint32_t out_format, void* hip_stream);
 
 /* ---- decoder: mp3.NewDecoder / io.Reader / io.Seeker (decode.go:27-388) ----
  * Scans on the host with read-ahead (headers, side info, reservoir) and
