@@ -586,6 +586,35 @@ int mp3g_scan_windows(uint32_t n_streams, const uint8_t* const* datas, const siz
   return MP3G_OK;
 }
 
+// The first frame the header walk accepts (tags skipped, sync search, the
+// pre-pass's version / layer / size checks): the frame NewDecoder takes the
+// sample rate from (decode.go:361-388).
+int mp3g_stream_rates(uint32_t n_streams, const uint8_t* const* datas, const size_t* lens, int n_threads, int* rates,
+                      int* channels) {
+  if (n_streams && (!datas || !lens)) return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "null argument");
+  const int nt = std::max(1, std::min<int>(n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency(),
+                                           (int)std::max<uint32_t>(1, n_streams)));
+  parallel_for(0, n_streams, nt, [&](uint32_t k) {
+    int rate = 0, nch = 0;
+    host::Source src;
+    src.data = datas[k];
+    src.len = (int64_t)lens[k];
+    if (src.skip_tags() == St::kOk) {
+      std::vector<host::WalkFrame> fr;
+      uint64_t ng = 0;
+      host::Source::Mark end_at;
+      (void)host::walk_frames(src, 1, &fr, &ng, &end_at);
+      if (!fr.empty()) {
+        rate = host::header_sample_rate(fr[0].header);
+        nch = ((fr[0].header >> 6) & 3u) == 3u ? 1 : 2;
+      }
+    }
+    if (rates) rates[k] = rate;
+    if (channels) channels[k] = nch;
+  });
+  return MP3G_OK;
+}
+
 int mp3g_scan_window_rows(const mp3g_scan* s, const mp3g_window_row** rows) {
   if (!s || !rows || !s->windowed) return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "not a windowed scan");
   *rows = s->rows.data();

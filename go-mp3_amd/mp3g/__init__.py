@@ -19,7 +19,8 @@ __all__ = ["CHANNEL_DTYPE", "GRANULE_DTYPE", "STREAM_DTYPE", "STATE_DTYPE", "MOD
            "parse_streams", "Decoder", "HJOB_DTYPE", "scan_streams", "huffman_execute", "HUFF_ROWS_COUNT1",
            "HUFF_STAGE_WIDE", "HUFF_STAGE_MID", "huffman_stage_flags", "decode_streams",
            "WINDOW_DTYPE", "WINDOW_ROW_DTYPE", "WINDOW_GAPLESS", "scan_windows", "WindowPlan",
-           "decode_windows_tensor"]
+           "decode_windows_tensor", "RESAMPLE_ROW_DTYPE", "RESAMPLE_FAST", "RESAMPLE_BEST", "Resampler",
+           "stream_rates", "decode_windows_resampled_tensor"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -134,6 +135,16 @@ def lib():
             L.mp3g_scan_window_rows.argtypes = [vp, C.POINTER(vp)]
             L.mp3g_plan_create_windows.argtypes = [C.c_int, vp, vp, u32, u32, u32, u32, C.POINTER(vp)]
             L.mp3g_plan_execute_windows.argtypes = [vp, vp, vp, vp, u32, vp]
+        if hasattr(L, "mp3g_resampler_create"):  # (an older build through MP3G_LIB: A/B runs)
+            L.mp3g_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                C.POINTER(vp)]
+            L.mp3g_resampler_free.argtypes = [vp]
+            L.mp3g_resampler_free.restype = None
+            L.mp3g_resampler_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(vp),
+                                              C.POINTER(u32)]
+            L.mp3g_resample_host.argtypes = [vp, vp, u64, u64, u64, u64, vp]
+            L.mp3g_resample_rows.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp]
+            L.mp3g_stream_rates.argtypes = [u32, vp, vp, C.c_int, vp, vp]
         L.mp3g_lame_parse.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo)]
         L.mp3g_lame_parse_reader.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo), C.POINTER(C.c_size_t)]
         L.mp3g_lame_total_delay.argtypes = [C.POINTER(_LameInfo)]
@@ -526,12 +537,18 @@ def scan_windows(datas, starts, n_samples, gapless=False, n_threads=0):
     [WINDOW_ROW_DTYPE]: lead (granules decoded with PCM off), skip (samples of
     the window's first granule in front of it) and n_valid (samples the row
     receives).  gapless: a bool, or one per stream."""
-    bufs, ptrs, lens = _stream_args(datas)
     win = np.zeros(max(1, len(datas)), WINDOW_DTYPE)
     win["start"][:len(datas)] = np.asarray(starts, dtype=np.uint64)
     win["n_samples"] = int(n_samples)
     win["flags"][:len(datas)] = np.where(np.broadcast_to(np.asarray(gapless, dtype=bool), (len(datas),)),
                                          WINDOW_GAPLESS, 0)
+    return _scan_windows(datas, win, n_threads)
+
+
+def _scan_windows(datas, win, n_threads=0):
+    """scan_windows on a window table [WINDOW_DTYPE] (mp3g_scan_windows takes a
+    length per stream; scan_windows gives every stream the same)."""
+    bufs, ptrs, lens = _stream_args(datas)
     h = C.c_void_p()
     t0 = time.perf_counter()
     _check(lib().mp3g_scan_windows(len(datas), ptrs, lens, _ptr(win), n_threads, C.byref(h)))
@@ -589,6 +606,194 @@ def decode_windows_tensor(datas, starts, n_samples, mode=MODE_EXACT, out_format=
         st.synchronize()
         plan.close()
     return batch, s["rows"]["n_valid"].astype(np.int64), s["end_status"]
+
+
+# ---- sample-rate conversion of decoded rows (include/mp3g.h) ----------------
+# one row of Resampler.rows (mp3g_resample_row)
+RESAMPLE_ROW_DTYPE = np.dtype([("out_start", "<u8"), ("src_origin", "<u8"), ("src_row", "<u4"), ("out_row", "<u4"),
+                               ("n_src", "<u4"), ("n_out", "<u4")])
+assert RESAMPLE_ROW_DTYPE.itemsize == 32
+RESAMPLE_MAX_TAPS = 1 << 18
+# the presets (resampy's kaiser_fast / kaiser_best): zeros, rolloff, beta
+RESAMPLE_FAST = (16, 0.85, 8.555504641634386)
+RESAMPLE_BEST = (64, 0.9475937167399596, 14.769656459379492)
+RESAMPLE_QUALITY = {"fast": RESAMPLE_FAST, "best": RESAMPLE_BEST}
+
+
+class Resampler:
+    """Polyphase windowed-sinc resampler fi -> fo (mp3g_resampler_*): y[n] is
+    ONE float32 FMA chain over 2 W taps in ascending order, so the device
+    call (rows) equals the host reference (host) bit for bit.  device=None (or
+    -1) makes a host-only object; fi == fo is a copy (W = 0, no taps)."""
+
+    def __init__(self, fi, fo, zeros=RESAMPLE_FAST[0], rolloff=RESAMPLE_FAST[1], beta=RESAMPLE_FAST[2], device=None):
+        self._h = C.c_void_p()
+        self.device = -1 if device is None else int(device)
+        self.fi, self.fo = int(fi), int(fo)
+        _check(lib().mp3g_resampler_create(self.device, self.fi, self.fo, int(zeros), float(rolloff), float(beta),
+                                           C.byref(self._h)))
+        a, b, c, t, p = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_void_p()
+        _check(lib().mp3g_resampler_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(p), C.byref(t)))
+        self.L, self.M, self.W, self.tile = a.value, b.value, c.value, t.value
+        n = self.L * 2 * self.W
+        # a view of the library's table: valid while this object lives
+        self.taps = (np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n,)).reshape(self.L, 2 * self.W)
+                     if n else np.zeros((self.L, 0), np.float32))
+        self._keep = None
+
+    def out_len(self, n_src):
+        """Samples of the resampled signal of n_src source samples: ceil(n L / M)."""
+        return -((-int(n_src) * self.L) // self.M)
+
+    def src_window(self, out_start, n_out):
+        """The source samples [a, b) the outputs [out_start, out_start + n_out)
+        read (a >= 0), n_out >= 1."""
+        s, T = int(out_start), int(n_out)
+        if self.W == 0:
+            return s, s + T
+        return max(0, s * self.M // self.L - self.W + 1), (s + T - 1) * self.M // self.L + self.W + 1
+
+    def host(self, src, src_origin, out_start, n_out):
+        """The reference on the CPU (mp3g_resample_host): outputs [out_start,
+        out_start + n_out) of the signal whose samples [src_origin, src_origin
+        + len(src)) are `src` (float32) and zero elsewhere."""
+        src = np.ascontiguousarray(src, dtype=np.float32)
+        out = np.zeros(int(n_out), np.float32)
+        _check(lib().mp3g_resample_host(self._h, _ptr(src) if len(src) else None, int(src_origin), len(src),
+                                        int(out_start), int(n_out), _ptr(out) if n_out else None))
+        return out
+
+    def rows(self, d_src, d_out, rows, stream=None):
+        """The device call (mp3g_resample_rows): d_src float32 [*, C, S] (or
+        [*, S]) and d_out float32 [*, C, T] (or [*, T]) contiguous tensors on
+        this resampler's device, C = 1 or 2; rows: RESAMPLE_ROW_DTYPE[n] (numpy:
+        uploaded and kept until the next call; or a uint8 device tensor of n *
+        32 bytes).  Writes the n_out samples of each row and plane, nothing
+        else.  Asynchronous on `stream` (a hipStream_t; None = the current
+        torch stream)."""
+        import torch
+        for t in (d_src, d_out):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() not in (2, 3) or not t.is_cuda:
+                raise ValueError("Resampler.rows: contiguous float32 device tensors [*, C, S] or [*, S]")
+        nch = d_out.shape[1] if d_out.dim() == 3 else 1
+        if (d_src.shape[1] if d_src.dim() == 3 else 1) != nch:
+            raise ValueError("Resampler.rows: source and output differ in channels")
+        if isinstance(rows, np.ndarray):
+            rows = np.ascontiguousarray(rows, dtype=RESAMPLE_ROW_DTYPE)
+            n = len(rows)
+            if n and (int(rows["src_row"].max()) >= d_src.shape[0] or int(rows["out_row"].max()) >= d_out.shape[0]
+                      or int(rows["n_src"].max()) > d_src.shape[-1] or int(rows["n_out"].max()) > d_out.shape[-1]):
+                raise ValueError("Resampler.rows: a row lies outside the tensors")
+            d_rows = torch.from_numpy(rows.view(np.uint8).copy()).to(d_out.device) if n else None
+        else:
+            d_rows, n = rows, rows.numel() // RESAMPLE_ROW_DTYPE.itemsize
+        self._keep = d_rows
+        if stream is None:
+            stream = torch.cuda.current_stream(d_out.device).cuda_stream
+        _check(lib().mp3g_resample_rows(self._h, C.c_void_p(d_src.data_ptr()), int(d_src.shape[-1]),
+                                        C.c_void_p(d_out.data_ptr()), int(d_out.shape[-1]), int(nch),
+                                        C.c_void_p(d_rows.data_ptr()) if n else None, n,
+                                        C.c_void_p(stream) if stream else None))
+        return d_rows
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.taps = None
+            lib().mp3g_resampler_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def stream_rates(datas, n_threads=0, channels=False):
+    """The sample rate of each stream's first valid frame (mp3g_stream_rates; 0:
+    no valid frame) as int32[B]; channels=True: (rates, channel counts)."""
+    bufs, ptrs, lens = _stream_args(datas)
+    rates = np.zeros(max(1, len(datas)), np.int32)
+    nch = np.zeros(max(1, len(datas)), np.int32)
+    _check(lib().mp3g_stream_rates(len(datas), ptrs, lens, n_threads, _ptr(rates), _ptr(nch)))
+    return (rates[:len(datas)], nch[:len(datas)]) if channels else rates[:len(datas)]
+
+
+def decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=MODE_EXACT, out_format=OUT_F32_PLANAR,
+                                    gapless=False, quality="fast", n_threads=0, device=0):
+    """decode_windows_tensor at ONE sample rate: starts[k] and n_samples count
+    samples at `rate`, and row k holds y_k[starts[k], starts[k] + lengths[k]),
+    zero-padded to n_samples, where y_k is the resample (Resampler, preset
+    `quality`: "fast" or "best", or a (zeros, rolloff, beta) tuple) of what the
+    windowed decode exposes as stream k -- its full decode, or with gapless the
+    trimmed one -- at the rate of its first valid frame (stream_rates).  A
+    stream already at `rate` is copied.  lengths[k] = ceil(N_k L / M) -
+    starts[k] clamped to [0, n_samples], N_k the stream's samples.
+
+    One windowed decode of all streams into an intermediate [B, C, T_src]
+    tensor (each stream's source window: Resampler.src_window), then one
+    Resampler.rows launch per distinct source rate; every sample equals
+    Resampler.host on the same slice of the full decode bit for bit.
+
+    Returns (batch, lengths, end_status, rates): batch [B, 2, n_samples]
+    (OUT_F32_PLANAR) or [B, n_samples] (OUT_F32_MONO) on cuda:device, lengths
+    int64[B], end_status of the windowed scan, rates int32[B] (0: no valid
+    frame, an all-zero row)."""
+    import torch
+    if out_format not in (OUT_F32_PLANAR, OUT_F32_MONO):
+        raise Mp3gError(8 if out_bytes_per_granule(out_format) else 1, "windowed output is OUT_F32_PLANAR or OUT_F32_MONO")
+    if int(rate) <= 0:
+        raise Mp3gError(1, "rate not positive")
+    zeros, rolloff, beta = RESAMPLE_QUALITY[quality] if isinstance(quality, str) else quality
+    B, T = len(datas), int(n_samples)
+    starts = [int(s) for s in starts]
+    if len(starts) != B or T < 0 or any(s < 0 for s in starts):
+        raise ValueError("decode_windows_resampled_tensor: one start >= 0 per stream")
+    rates = stream_rates(datas, n_threads=n_threads)
+    rs = {int(f): Resampler(int(f), int(rate), zeros, rolloff, beta, device=device) for f in set(rates.tolist()) if f}
+    dev = torch.device("cuda", device)
+    planar = out_format == OUT_F32_PLANAR
+    batch = torch.zeros((B, 2, T) if planar else (B, T), dtype=torch.float32, device=dev)
+    lengths = np.zeros(B, np.int64)
+    win = np.zeros(max(1, B), WINDOW_DTYPE)
+    win["flags"][:B] = np.where(np.broadcast_to(np.asarray(gapless, dtype=bool), (B,)), WINDOW_GAPLESS, 0)
+    for k in range(B):
+        if rates[k] and T:
+            a, b = rs[int(rates[k])].src_window(starts[k], T)
+            if b - a > (1 << 26):
+                raise Mp3gError(1, "source window of more than MP3G_WINDOW_MAX_SAMPLES samples")
+            win["start"][k], win["n_samples"][k] = a, b - a
+    s = _scan_windows(datas, win, n_threads)
+    n, T_src = len(s["granules"]), int(win["n_samples"].max())
+    if n:
+        d_g = torch.from_numpy(s["granules"].view(np.uint8)).to(dev)
+        d_j = torch.from_numpy(s["jobs"].view(np.uint8)).to(dev)
+        d_m = torch.from_numpy(s["main_data"]).to(dev)
+        d_c = torch.empty(n * 1152, dtype=torch.int16, device=dev)
+        inter = torch.zeros((B, 2, T_src) if planar else (B, T_src), dtype=torch.float32, device=dev)
+        plan = WindowPlan(s["streams"], s["rows"], T_src, mode=mode, device=device)
+        st = torch.cuda.current_stream(dev)
+        flags = HUFF_ROWS_COUNT1 | huffman_stage_flags(s["jobs"], n)
+        huffman_execute(d_j, n, d_m, d_g, d_c, stream=st.cuda_stream, device=device, flags=flags)
+        plan.execute(d_g, d_c, inter, stream=st.cuda_stream, out_format=out_format)
+        n_valid = s["rows"]["n_valid"].astype(np.int64)
+        for f, r in rs.items():
+            ks = [k for k in range(B) if rates[k] == f and n_valid[k] > 0]
+            rows = np.zeros(len(ks), RESAMPLE_ROW_DTYPE)
+            for i, k in enumerate(ks):
+                a, want = int(win["start"][k]), int(win["n_samples"][k])
+                # fewer samples than asked for: the stream ends at N = a + n_valid
+                ln = T if n_valid[k] >= want else min(T, max(0, r.out_len(a + int(n_valid[k])) - starts[k]))
+                lengths[k] = ln
+                rows[i] = (starts[k], a, k, k, int(n_valid[k]), ln)
+            rows = rows[rows["n_out"] > 0]
+            if len(rows):
+                r.rows(inter, batch, rows, stream=st.cuda_stream)
+        st.synchronize()
+        plan.close()
+    for r in rs.values():
+        r.close()
+    return batch, lengths, s["end_status"], rates
 
 
 def _host_buffer(out, want_int16, want_float32=False):

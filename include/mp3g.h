@@ -51,7 +51,9 @@ extern "C" {
  *    formats MP3G_OUT_S16_MONO / MP3G_OUT_F32_MONO and
  *    mp3g_decode_streams_into_out; sample-windowed decode into dense rows --
  *    mp3g_scan_windows, mp3g_scan_window_rows, mp3g_plan_create_windows and
- *    mp3g_plan_execute_windows.) */
+ *    mp3g_plan_execute_windows; sample-rate conversion of decoded rows --
+ *    mp3g_resampler_*, mp3g_resample_host, mp3g_resample_rows and
+ *    mp3g_stream_rates.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -540,6 +542,81 @@ int mp3g_plan_create_windows(int device, const mp3g_stream* streams, const mp3g_
  * mp3g_plan_execute). */
 int mp3g_plan_execute_windows(mp3g_plan* plan, const mp3g_granule* d_granules, const int16_t* d_coeffs,
                               void* d_out, uint32_t out_format, void* hip_stream);
+
+/* ---- sample-rate conversion of decoded rows --------------------------------
+ * A polyphase windowed-sinc resampler for the float rows the windowed decode
+ * delivers: MP3 streams come at 32 / 44.1 / 48 kHz (MPEG-1) or 16 / 22.05 /
+ * 24 kHz (MPEG-2) and a model wants one rate.  No reference counterpart:
+ * go-mp3 delivers every stream at its own rate (decode.go:137-140).
+ *
+ * Filter.  For source rate fi and target rate fo: g = gcd(fi, fo), M = fi / g,
+ * L = fo / g, c = rolloff * min(1, L / M) (cutoff relative to the source
+ * Nyquist), W = ceil(zeros / c) (half width in source samples) and
+ *   h[r][k] = c sinc(c t) kaiser(t / W),  t = k - (W - 1) - r / L,
+ *   sinc(u) = sin(pi u) / (pi u),  kaiser(u) = I0(beta sqrt(1 - u^2)) / I0(beta)
+ * for r in [0, L), k in [0, 2W), computed in float64 and rounded once to
+ * float32; no per-phase normalisation.  zeros outside 1..64 or a table of more
+ * than MP3G_RESAMPLE_MAX_TAPS entries is MP3G_ERR_UNSUPPORTED, a rate <= 0 or a
+ * rolloff outside (0, 1] MP3G_ERR_INVALID_ARGUMENT, before any device call.
+ *
+ * Signal.  x is zero outside [0, N).  For output n, (q, r) = divmod(n M, L)
+ * (64-bit; n M / L < 2^63) and
+ *   acc = +0.0f;  for k = 0 .. 2W-1: acc = fmaf(h[r][k], x[q - W + 1 + k], acc)
+ *   y[n] = acc
+ * -- ONE float32 FMA chain in ascending k.  The order is part of the contract:
+ * the device call equals mp3g_resample_host bit for bit, whatever the tiling.
+ * (Taps on samples outside [0, N) may be skipped: the accumulator starts at +0
+ * and never becomes -0.)  y has ceil(N L / M) samples.  fi == fo is a copy:
+ * y = x, L = M = 1, W = 0, no taps. */
+#define MP3G_RESAMPLE_MAX_TAPS (1u << 18)
+#define MP3G_RESAMPLE_FAST_ZEROS 16 /* resampy's kaiser_fast */
+#define MP3G_RESAMPLE_FAST_ROLLOFF 0.85
+#define MP3G_RESAMPLE_FAST_BETA 8.555504641634386
+#define MP3G_RESAMPLE_BEST_ZEROS 64 /* resampy's kaiser_best */
+#define MP3G_RESAMPLE_BEST_ROLLOFF 0.9475937167399596
+#define MP3G_RESAMPLE_BEST_BETA 14.769656459379492
+typedef struct mp3g_resampler mp3g_resampler;
+/* Builds the table; device >= 0 also uploads it to that device (once), device
+ * = -1 makes a host-only object (mp3g_resample_host, mp3g_resampler_info). */
+int mp3g_resampler_create(int device, int fi, int fo, int zeros, double rolloff, double beta,
+                          mp3g_resampler** out);
+void mp3g_resampler_free(mp3g_resampler* r);
+/* L, M, W, the host table float [L][2W] (owned by the resampler; NULL for a
+ * copy) and the device call's output tile length (any may be NULL). */
+int mp3g_resampler_info(const mp3g_resampler* r, uint32_t* L, uint32_t* M, uint32_t* W, const float** taps,
+                        uint32_t* tile);
+/* The definition above in plain C++ (the reference the device call equals):
+ * source sample j is src[j - src_origin] for src_origin <= j < src_origin +
+ * n_src and 0 otherwise; writes y[out_start .. out_start + n_out) to `out`. */
+int mp3g_resample_host(const mp3g_resampler* r, const float* src, uint64_t src_origin, uint64_t n_src,
+                       uint64_t out_start, uint64_t n_out, float* out);
+/* One row of the device call: outputs y[out_start, out_start + n_out) of the
+ * signal whose samples [src_origin, src_origin + n_src) are row src_row of
+ * the source (zero elsewhere), to the first n_out floats of row out_row of the
+ * output.  32 bytes. */
+typedef struct mp3g_resample_row {
+  uint64_t out_start;
+  uint64_t src_origin;
+  uint32_t src_row;
+  uint32_t out_row;
+  uint32_t n_src; /* <= src_stride */
+  uint32_t n_out; /* <= out_stride */
+} mp3g_resample_row;
+/* d_src: float [*][n_channels][src_stride], d_out: float [*][n_channels]
+ * [out_stride], n_channels 1 or 2 (every plane of a row is resampled alike);
+ * d_rows: n_rows descriptors.  All three are device pointers and the launch
+ * shape depends on none of their contents: asynchronous on hip_stream and
+ * graph-capturable.  Writes the n_out samples of each row and plane and
+ * nothing else; a row whose n_out exceeds out_stride is cut at out_stride. */
+int mp3g_resample_rows(const mp3g_resampler* r, const float* d_src, uint32_t src_stride, float* d_out,
+                       uint32_t out_stride, uint32_t n_channels, const mp3g_resample_row* d_rows,
+                       uint32_t n_rows, void* hip_stream);
+/* The sample rate of each stream's first valid frame (after tags and the sync
+ * search, as mp3g_decoder_info reports it; found by the header walk, no side
+ * info parsed) and its channel count (1 / 2; either output may be NULL).  A
+ * stream without a valid frame gets 0 and 0. */
+int mp3g_stream_rates(uint32_t n_streams, const uint8_t* const* datas, const size_t* lens, int n_threads,
+                      int* rates, int* channels);
 
 /* ---- decoder: mp3.NewDecoder / io.Reader / io.Seeker (decode.go:27-388) ----
  * Scans on the host with read-ahead (headers, side info, reservoir) and
