@@ -24,10 +24,7 @@ int ensure_device_ready(int device);
 int plan_chunks(int device, const mp3g_stream* streams, uint32_t n_streams, uint32_t granules_per_chunk,
                 uint32_t mode, std::vector<ChunkDesc>* chunks, uint64_t* n_granules, uint64_t* n_halo);
 struct ZoneScratch;  // kernels.h
-int plan_launch(uint32_t mode, const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
-                const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out, int16_t* d_pcm,
-                const ZoneScratch* zones, hipStream_t stream);
-// The same with an output format (MP3G_OUT_*; plan_launch is MP3G_OUT_S16).
+// (out_format: MP3G_OUT_*)
 int plan_launch_out(uint32_t mode, const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
                     const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out, void* d_out,
                     uint32_t out_format, const ZoneScratch* zones, hipStream_t stream);

@@ -35,18 +35,14 @@
 // start and overwrites its PCM: within +-1 LSB on every valid input.  (The
 // in-wave pass with the *_exact functions is compiled into the diagnostic
 // kStamp build only.)
-// (compiled in its own TU, kernels_fast.hip)
+// (compiled in its own TU, kernels_fast.hip, after granule_out.hip: the PCM
+// output stage -- pack_granule / store_granule -- and lane_fresh are there)
 #pragma clang fp contract(fast)
 #include <type_traits>
 
 #include "dct32.h"
 #include "dct4_18.h"
 #include "xlane.h"
-
-// cache policy of the PCM stores (2 = nt: streamed past the caches)
-#ifndef MP3G_PCM_STORE_AUX
-#define MP3G_PCM_STORE_AUX 2
-#endif
 
 namespace mp3g {
 namespace v3 {
@@ -63,10 +59,7 @@ namespace v3 {
 // bands' scale factors by ds_bpermute -- no LDS round trip and no LDS copy of
 // the next descriptors per granule.  The rare paths that index the scale
 // factors per line (short blocks, intensity stereo) first drop the descriptor
-// into the wave's LDS slot.  0: the descriptors staged in LDS (round 5).
-#ifndef MP3G_FAST_DESC_VGPR
-#define MP3G_FAST_DESC_VGPR 1
-#endif
+// into the wave's LDS slot.  (Round 5 staged the next descriptor in LDS.)
 #ifndef MP3G_FAST_WG_WAVES
 #define MP3G_FAST_WG_WAVES 8
 #endif
@@ -115,15 +108,6 @@ constexpr int kHist = 16;
 #endif
 constexpr int kSlots = kHist + 18;
 static_assert(kSlots == kFastRingSlots, "FastTables::sinfo indexes the staged ring");
-#ifndef MP3G_FAST_PCM_D16
-#define MP3G_FAST_PCM_D16 0  // (A/B) PCM as per-channel 16-bit stores instead of swap + merge
-#endif
-#ifndef MP3G_FAST_P43
-#define MP3G_FAST_P43 1  // long-block requantize through the p43 LDS table (0: arithmetic, A/B)
-#endif
-#ifndef MP3G_P43_SCHED
-#define MP3G_P43_SCHED 0
-#endif
 #ifndef MP3G_FAST_DWIN_STRIDE
 #define MP3G_FAST_DWIN_STRIDE 20
 #endif
@@ -167,15 +151,14 @@ struct __align__(16) WaveSmem {
   // turns them into X in place; before that they stage the raw coefficients
   // of short-block granules (reorder gather) and the intensity-stereo pass
   float ring[2][32][kSlots];
-  mp3g_granule desc;  // 16-B aligned: the channels' first 8 bytes are one 8-B read each
-  // the next granule's descriptor, one granule ahead: its count1s bound the
+  // the current granule's descriptor, for the paths that index it per line
+  // (16-B aligned: the channels' first 8 bytes are one 8-B read each).  The
+  // next granule's stays in a VGPR (dvn in the kernel): its count1s bound the
   // next granule's coefficient prefetch (lines at and above count1 are zero by
   // the parse's guarantee, maindata/huffman.go:127-134, so they are neither
   // read here nor written by the main-data kernel, MP3G_HUFF_ROWS_COUNT1;
   // c3 -0.4 % against whole rows, tools/gpu_r03z.sh)
-#if !MP3G_FAST_DESC_VGPR
-  mp3g_granule descn;
-#endif
+  mp3g_granule desc;
   // requantization exponents n4 / 4 (float16, exact) of the long bands
   // [ch][sfb] and short bands [ch][sfb][win]; in the fast loop's all-long
   // granules the long bands' gains 2^(n4 / 4) as float32 [ch][sfb] instead
@@ -215,9 +198,8 @@ __device__ __forceinline__ void load_lines(const int16_t* coef, uint32_t g, int 
 // 0 for a channel the granule does not have): lines >= count1 are zero (the
 // bitstream parse's guarantee, maindata/huffman.go:127-134, which mp3g_validate
 // checks), so a 6-line piece starting at or above it is not fetched -- its
-// offset is pushed past the records and the load returns 0 without touching
-// memory.  At 128 kbps about 40 % of the coefficient bytes are skipped.
-constexpr int kNoRecord = 0x40000000;
+// offset is pushed past the records (kNoRecord) and the load returns 0 without
+// touching memory.  At 128 kbps about 40 % of the coefficient bytes are skipped.
 __device__ __forceinline__ void load_lines_lim(const int16_t* coef, uint32_t g, int lane, uint32_t cw[9], int nbytes,
                                                int lim) {
   const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
@@ -358,17 +340,6 @@ __device__ __forceinline__ float requant_fast(int xi, _Float16 e) {
 __device__ __forceinline__ float requant_gain(uint32_t xw, float g) {
   const float xf = (float)(int16_t)xw;
   return xf * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(fabsf(xf)) * (1.0f / 3.0f)) * g;
-}
-
-// The lane id, recomputed where it is used (asm volatile: not hoisted out of
-// the granule loop).  Values derived from it once and kept for the whole loop
-// cost a VGPR each; at the 128-VGPR budget the allocator spilled some to
-// scratch, and a reload is a VMEM load whose s_waitcnt also waits for the
-// in-flight PCM stores and prefetch.
-__device__ __forceinline__ int lane_fresh() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
 }
 
 // X of a V block: X[m] = V[m-16] (m >= 16), -V[48-m] (m < 16).
@@ -908,317 +879,6 @@ __device__ __forceinline__ void imdct_fast(const float x[18], int bt, int nch, b
   }
 }
 
-// (L, R) sample pairs without LDS staging: one v_permlane32_swap per slot
-// pair hands lane i slot 2p's (L, R) and lane 32 + i slot 2p + 1's, so every
-// lane stores one dword per slot pair and the wave 2 x 128 contiguous bytes.
-// Mono: the swap hands lane i channel 0's slot 2p and lane 32 + i its slot
-// 2p + 1, stored in both halves (frame.go:671-678).  acc2 holds sum * 32767.
-__device__ __forceinline__ void pack_pcm(const f2 acc2[9], int nch, uint32_t pk[9]) {
-  auto pack = [&](auto mono) {
-#pragma unroll
-    for (int p = 0; p < 9; p++) {
-      // int(sum * 32767) clamped to +-32767 (frame.go:663-669); no decodable
-      // input gets near NaN or |t| >= 2^63 (|sum| < 1e12)
-      const int a = (int)__builtin_amdgcn_fmed3f(acc2[p].x, -32767.0f, 32767.0f);
-      const int b = (int)__builtin_amdgcn_fmed3f(acc2[p].y, -32767.0f, 32767.0f);
-      const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-      // low halves of (r[0], r[1]) -> one dword: L | R << 16 (R = L for mono)
-      pk[p] = __builtin_amdgcn_perm((uint32_t)(decltype(mono)::value ? r[0] : r[1]), (uint32_t)r[0], 0x05040100u);
-    }
-  };
-  if (nch == 2) pack(std::false_type{});
-  else pack(std::true_type{});
-}
-
-// PCM of granule g: one dword per lane and slot pair, non-temporal (c2
-// -1.9 %, c3 -0.8 %).  Issued for replayed granules too, through a resource
-// with no records (straight-line vmcnt accounting).
-__device__ __forceinline__ void store_pcm(int16_t* pcm, uint32_t g, bool out, const uint32_t pk[9], int hi, int k) {
-  const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-      pcm + (size_t)g * 1152, (short)0, out ? MP3G_PCM_BYTES_PER_GRANULE : 0, 0x00020000);
-#pragma unroll
-  for (int p = 0; p < 9; p++)
-    __builtin_amdgcn_raw_buffer_store_b32(pk[p], rp, 4 * (32 * (2 * p + hi) + k), 0, MP3G_PCM_STORE_AUX);
-}
-
-// ---- float32 output (MP3G_OUT_F32 / MP3G_OUT_F32_PLANAR) ----
-// The window leaves lane (ch, k) slots 2p and 2p + 1 of output k in acc2[p]
-// (sum * 32767): the float sample is the s16 sample's clamp without the
-// truncation, scaled by 2^-15 (exact), so trunc(f * 32768) is the s16 sample.
-// A float store from this layout needs no cross-lane pack.  Mono: channel 0's
-// values go to the channel-1 lanes (v_permlane32_swap of a value with itself
-// hands every lane the low half's), which then write them to the other
-// channel / plane (frame.go:671-678).
-#ifndef MP3G_F32_STORE_SWAP
-#define MP3G_F32_STORE_SWAP 0  // (A/B) interleaved: swap + one 64-bit (L, R) store per slot pair
-#endif
-__device__ __forceinline__ void pack_pcm(const f2 acc2[9], int nch, float pf[18]) {
-#pragma unroll
-  for (int p = 0; p < 9; p++) {
-    pf[2 * p] = __builtin_amdgcn_fmed3f(acc2[p].x, -32767.0f, 32767.0f) * (1.0f / 32768.0f);
-    pf[2 * p + 1] = __builtin_amdgcn_fmed3f(acc2[p].y, -32767.0f, 32767.0f) * (1.0f / 32768.0f);
-  }
-  if (nch != 2) {  // (wave-uniform)
-#pragma unroll
-    for (int i = 0; i < 18; i++) {
-      const uint32_t u = __builtin_bit_cast(uint32_t, pf[i]);
-      pf[i] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_permlane32_swap(u, u, false, false)[0]);
-    }
-  }
-}
-
-// Where a chunk's stream lies (planar output: ChunkDesc::stream_first / stream_n).
-struct StreamGeom {
-  uint32_t first, n;
-};
-
-// Float samples of granule g, one dword per lane and slot, non-temporal like
-// the s16 stores and issued for replayed granules too (no records).
-//   F32:    float [g][32 slot + k][ch]: a store covers 256 contiguous bytes;
-//           the resource spans the granule's block (4,608 B).
-//   planar: plane(ch) + 576 (g - first) + 32 slot + k: two 128-B runs; the
-//           resource starts at the granule's place in plane 0 and ends with
-//           its place in plane 1 (the lane offset n * 2304 + 2300 stays below
-//           2^31: MP3G_PLANAR_MAX_GRANULES).
-template <int kFmt>
-__device__ __forceinline__ void store_pcm_f32(int16_t* pcm, StreamGeom sg, uint32_t g, bool out, const float pf[18],
-                                              int ch, int k) {
-  float* const o = reinterpret_cast<float*>(pcm);
-  if constexpr (kFmt == (int)MP3G_OUT_F32) {
-    const __amdgpu_buffer_rsrc_t rp =
-        __builtin_amdgcn_make_buffer_rsrc(o + (size_t)g * 1152, (short)0, out ? 2 * MP3G_PCM_BYTES_PER_GRANULE : 0, 0x00020000);
-#if MP3G_F32_STORE_SWAP
-    typedef uint32_t u2v __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int p = 0; p < 9; p++) {
-      // as the s16 pack: lane i gets slot 2p's (L, R), lane 32 + i slot 2p + 1's
-      // (mono: pack_pcm has made both channels equal already)
-      const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, pf[2 * p]),
-                                                      __builtin_bit_cast(uint32_t, pf[2 * p + 1]), false, false);
-      const u2v v = {(uint32_t)r[0], (uint32_t)r[1]};
-      __builtin_amdgcn_raw_buffer_store_b64(v, rp, 8 * (32 * (2 * p + ch) + k), 0, MP3G_PCM_STORE_AUX);
-    }
-#else
-#pragma unroll
-    for (int sl = 0; sl < 18; sl++)
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[sl]), rp, 8 * (32 * sl + k) + 4 * ch, 0,
-                                            MP3G_PCM_STORE_AUX);
-#endif
-  } else {
-    const uint32_t plane = sg.n * (uint32_t)MP3G_PCM_BYTES_PER_GRANULE;  // bytes of one plane
-    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-        o + (size_t)sg.first * 1152 + (size_t)(g - sg.first) * MP3G_LINES, (short)0,
-        out ? (int)(plane + MP3G_PCM_BYTES_PER_GRANULE) : 0, 0x00020000);
-    const int base = (int)(ch ? plane : 0u) + 4 * k;
-#pragma unroll
-    for (int sl = 0; sl < 18; sl++)
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[sl]), rp, base + 128 * sl, 0,
-                                            MP3G_PCM_STORE_AUX);
-  }
-}
-
-// ---- mono downmix output (MP3G_OUT_S16_MONO / MP3G_OUT_F32_MONO) ----
-// The s16 pack's v_permlane32_swap brings the two channels of a sample into
-// one lane: lane i holds slot 2p's (L, R), lane 32 + i slot 2p + 1's.  The
-// downmix is one add there, and every lane owns ONE sample per slot pair:
-// sample 64 p + lane of the granule's 576, so a store of the wave covers 64
-// consecutive samples.
-//   s16:   m = (L + R) >> 1 on the s16 samples (arithmetic shift: floor)
-//   float: m = (fL + fR) * 0.5f on the float samples (one rounded add; the
-//          halving is exact)
-// A mono granule gives channel 0's sample as it is (wave-uniform branch).
-constexpr bool fmt_is_mono(int fmt) {
-  return fmt == (int)MP3G_OUT_S16_MONO || fmt == (int)MP3G_OUT_F32_MONO || fmt == kFmtWinMono;
-}
-// the windowed formats (kernels.h): float planar / float mono samples placed
-// with sample granularity into dense rows
-constexpr bool fmt_is_windowed(int fmt) { return fmt == kFmtWinPlanar || fmt == kFmtWinMono; }
-#ifndef MP3G_MONO_S16_PACK
-#define MP3G_MONO_S16_PACK 0  // (A/B) s16 mono: pair neighbouring lanes' samples (one DPP move), dword stores from the even lanes
-#endif
-__device__ __forceinline__ void pack_pcm_mono(const f2 acc2[9], int nch, uint32_t pm[9]) {
-  auto pack = [&](auto mono) {
-#pragma unroll
-    for (int p = 0; p < 9; p++) {
-      const int a = (int)__builtin_amdgcn_fmed3f(acc2[p].x, -32767.0f, 32767.0f);
-      const int b = (int)__builtin_amdgcn_fmed3f(acc2[p].y, -32767.0f, 32767.0f);
-      const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-      const int m = decltype(mono)::value ? (int)r[0] : ((int)r[0] + (int)r[1]) >> 1;
-#if MP3G_MONO_S16_PACK
-      // lane 2j takes lane 2j + 1's sample (quad_perm [1, 1, 3, 3]) into its high half
-      const int n = __builtin_amdgcn_update_dpp(0, m, 0xF5, 0xf, 0xf, false);
-      pm[p] = __builtin_amdgcn_perm((uint32_t)n, (uint32_t)m, 0x05040100u);
-#else
-      pm[p] = (uint32_t)m;
-#endif
-    }
-  };
-  if (nch == 2) pack(std::false_type{});
-  else pack(std::true_type{});
-}
-
-__device__ __forceinline__ void pack_pcm_mono(const f2 acc2[9], int nch, float pm[9]) {
-  auto pack = [&](auto mono) {
-#pragma unroll
-    for (int p = 0; p < 9; p++) {
-      const float a = __builtin_amdgcn_fmed3f(acc2[p].x, -32767.0f, 32767.0f) * (1.0f / 32768.0f);
-      const float b = __builtin_amdgcn_fmed3f(acc2[p].y, -32767.0f, 32767.0f) * (1.0f / 32768.0f);
-      const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b),
-                                                      false, false);
-      const float fl = __builtin_bit_cast(float, (uint32_t)r[0]), fr = __builtin_bit_cast(float, (uint32_t)r[1]);
-      pm[p] = decltype(mono)::value ? fl : (fl + fr) * 0.5f;
-    }
-  };
-  if (nch == 2) pack(std::false_type{});
-  else pack(std::true_type{});
-}
-
-// The registers a lane hands the store stage, per format: s16 (L, R) dwords,
-// the lane's 18 float samples, or one mono sample per slot pair.
-template <int kFmt>
-struct PcmRegs {
-  typedef float type[18];
-};
-template <>
-struct PcmRegs<(int)MP3G_OUT_S16> {
-  typedef uint32_t type[9];
-};
-template <>
-struct PcmRegs<(int)MP3G_OUT_S16_MONO> {
-  typedef uint32_t type[9];
-};
-template <>
-struct PcmRegs<(int)MP3G_OUT_F32_MONO> {
-  typedef float type[9];
-};
-template <>
-struct PcmRegs<kFmtWinMono> {
-  typedef float type[9];
-};
-
-// Mono samples of granule g: sample 64 p + lane, non-temporal and issued for
-// replayed granules too (no records), nine stores per lane like the s16 path.
-// The resource spans exactly the granule: 1,152 B (s16) or 2,304 B (float).
-//   s16:   16-bit stores, 128 contiguous bytes per store of the wave
-//          (MP3G_MONO_S16_PACK: dwords from the even lanes; the odd lanes'
-//          offset lies past the records)
-//   float: one dword per lane, 256 contiguous bytes
-__device__ __forceinline__ void store_pcm_mono(int16_t* pcm, uint32_t g, bool out, const uint32_t pm[9], int lane) {
-  const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-      pcm + (size_t)g * MP3G_LINES, (short)0, out ? MP3G_PCM_BYTES_PER_GRANULE / 2 : 0, 0x00020000);
-#if MP3G_MONO_S16_PACK
-  const int off = (lane & 1) ? kNoRecord : 2 * lane;
-#pragma unroll
-  for (int p = 0; p < 9; p++) __builtin_amdgcn_raw_buffer_store_b32(pm[p], rp, off + 128 * p, 0, MP3G_PCM_STORE_AUX);
-#else
-#pragma unroll
-  for (int p = 0; p < 9; p++)
-    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)pm[p], rp, 2 * (64 * p + lane), 0, MP3G_PCM_STORE_AUX);
-#endif
-}
-
-__device__ __forceinline__ void store_pcm_mono(int16_t* pcm, uint32_t g, bool out, const float pm[9], int lane) {
-  const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<float*>(pcm) + (size_t)g * MP3G_LINES, (short)0, out ? MP3G_PCM_BYTES_PER_GRANULE : 0, 0x00020000);
-#pragma unroll
-  for (int p = 0; p < 9; p++)
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pm[p]), rp, 4 * (64 * p + lane), 0,
-                                          MP3G_PCM_STORE_AUX);
-}
-
-// ---- windowed output (kFmtWinPlanar / kFmtWinMono, kernels.h WindowRow) ----
-// The registers are those of the float planar / float mono formats; only the
-// placement differs: sample i of granule g goes to row index r = 576 (g - lo)
-// - skip + i when 0 <= r < n_valid.  The resource starts at the row (plane 0)
-// and spans it up to the last valid sample of its last plane; as many stores
-// as the other formats, replayed granules included (no records).  Every lane
-// is masked explicitly, by forcing its offset to kNoRecord:
-//   * the shift is negative in the window's first granule -- it is part of
-//     the VECTOR offset, never of the scalar offset operand, and a lane in
-//     front of the row is masked before its offset could wrap;
-//   * the range check alone cannot clip plane 0 at n_valid (the next bytes are
-//     plane 1's, or the next row's).
-// kNoRecord (2^30) lies past the records: 8 T <= 2^29 (MP3G_WINDOW_MAX_SAMPLES).
-// The mask is an add, a compare and a select per store.  A granule wholly
-// inside the window (a wave-uniform test) takes an unmasked path instead, the
-// slot as the instruction's immediate offset like the plain formats; both
-// paths issue the same number of stores.  The ISA and the measurement pull in
-// opposite directions here, and the measurement decides (DESIGN.md section
-// 9b): with two store sequences joining in front of the loop's back edge the
-// wait-count pass turns the back edge's s_waitcnt vmcnt(18) -- wait for the
-// prefetch, leave the 18 stores in flight, section 6 -- into vmcnt(0), yet
-// full-length windows run 2.1 % faster in the fast kernel and the 2-second
-// windows of c3 4.6 % faster than with every store masked
-// (-DMP3G_WIN_INSIDE_PATH=0: one straight line of masked stores, vmcnt(18)
-// kept): on this issue-bound kernel the 54 VALU instructions of the masks cost
-// more than the wait, which the SIMD's other waves cover.
-#ifndef MP3G_WIN_INSIDE_PATH
-#define MP3G_WIN_INSIDE_PATH 1
-#endif
-// The row of a chunk's stream as wave-uniform scalars, loaded once per chunk
-// -- in front of the granule loop and of the chunk's first store, so the
-// loads are settled with the prologue's (a load inside the loop would make the
-// store stage wait for the previous granule's stores).  off0 = 576 lo + skip
-// modulo 2^32: sample i of granule g has row index 576 g - off0 + i.
-struct WinGeom {
-  float* o;  // the row's first float (plane 0)
-  uint32_t off0, nv, plane;
-};
-__device__ __forceinline__ WinGeom win_geom(int16_t* pcm, const void* table, uint32_t stream) {
-  const WindowRow* row = static_cast<const WindowRow*>(table) + stream;
-  const uint64_t base = row->base;
-  const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)base);
-  const uint32_t bhi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
-  return WinGeom{reinterpret_cast<float*>(pcm) + (((uint64_t)bhi << 32) | blo),
-                 (uint32_t)__builtin_amdgcn_readfirstlane(576u * row->lo + row->skip),
-                 (uint32_t)__builtin_amdgcn_readfirstlane(row->n_valid),
-                 (uint32_t)__builtin_amdgcn_readfirstlane(row->plane)};
-}
-
-template <int kFmt>
-__device__ __forceinline__ void store_pcm_win(const WinGeom& wg, uint32_t g, bool out, const float* pf, int lane) {
-  const uint32_t nv = wg.nv;
-  const int shift = (int)(576u * g - wg.off0);
-  // (wave-uniform; constant false with -DMP3G_WIN_INSIDE_PATH=0)
-  const bool inside = MP3G_WIN_INSIDE_PATH && shift >= 0 && (uint32_t)shift + 576u <= nv;
-  if constexpr (kFmt == kFmtWinPlanar) {
-    const uint32_t plane = wg.plane;
-    const __amdgpu_buffer_rsrc_t rp =
-        __builtin_amdgcn_make_buffer_rsrc(wg.o, (short)0, out ? (int)(4u * (plane + nv)) : 0, 0x00020000);
-    const int r0 = shift + (lane & 31);
-    const int b4 = 4 * ((lane >> 5 ? (int)plane : 0) + r0);
-    if (inside) {
-#pragma unroll
-      for (int sl = 0; sl < 18; sl++)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[sl]), rp, b4 + 128 * sl, 0,
-                                              MP3G_PCM_STORE_AUX);
-    } else {
-#pragma unroll
-      for (int sl = 0; sl < 18; sl++)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[sl]), rp,
-                                              (uint32_t)(r0 + 32 * sl) < nv ? b4 + 128 * sl : kNoRecord, 0,
-                                              MP3G_PCM_STORE_AUX);
-    }
-  } else {
-    const __amdgpu_buffer_rsrc_t rp =
-        __builtin_amdgcn_make_buffer_rsrc(wg.o, (short)0, out ? (int)(4u * nv) : 0, 0x00020000);
-    const int r0 = shift + lane;
-    const int b4 = 4 * r0;
-    if (inside) {
-#pragma unroll
-      for (int p = 0; p < 9; p++)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[p]), rp, b4 + 256 * p, 0,
-                                              MP3G_PCM_STORE_AUX);
-    } else {
-#pragma unroll
-      for (int p = 0; p < 9; p++)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pf[p]), rp,
-                                              (uint32_t)(r0 + 64 * p) < nv ? b4 + 256 * p : kNoRecord, 0,
-                                              MP3G_PCM_STORE_AUX);
-    }
-  }
-}
-
 // Entry state of a replay start: overlap store in registers, V history as X
 // vectors, from the stream's state_in (init_in) or zero.  stp[q] =
 // (store[q], store[17-q]), each element times the frequency-inversion sign of
@@ -1445,7 +1105,6 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
   WinGeom wgeom = {nullptr, 0u, 0u, 0u};
   if constexpr (fmt_is_windowed(kFmt)) wgeom = win_geom(pcm, state_out, cd.stream);
 
-
   // entry state: overlap store in registers, V history as X vectors
   // IMDCT overlap `store` (frame.go:473-476) in registers as pairs
   // stp[q] = (store[q], store[17-q]), each element times the frequency-inversion
@@ -1470,7 +1129,6 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
   }
 
   uint32_t cw[9] = {};  // the current granule's raw coefficients (lane's 18 lines)
-#if MP3G_FAST_DESC_VGPR
   // the descriptors of the current and the next granule, one dword per lane
   uint32_t dv = 0, dvn = 0;
   if (w < end) {
@@ -1478,14 +1136,6 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     dv = load_desc_dword(gran, w, lane, true);
     dvn = load_desc_dword(gran, w + 1, lane, w + 1 < end);
   }
-#else
-  if (w < end) {
-    load_lines_lim(coef, w, lane, cw, (int)(MP3G_COEF_PER_GRANULE * sizeof(int16_t)), count1_lim(gran, w, lane));
-    if (lane < 10) reinterpret_cast<uint4*>(&s.desc)[lane] = reinterpret_cast<const uint4*>(gran + w)[lane];
-    if (lane < 10 && w + 1 < end)
-      reinterpret_cast<uint4*>(&s.descn)[lane] = reinterpret_cast<const uint4*>(gran + w + 1)[lane];
-  }
-#endif
   shared_init();
   // The loads above (coefficients, dv, dvn, entry state) settled here, once per
   // chunk.  Left in flight, they reach the granule loop's header as pending
@@ -1551,103 +1201,28 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     geom = StreamGeom{(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)cd.stream_first),
                       (uint32_t)__builtin_amdgcn_readfirstlane(cd.stream_n)};
   auto window_store = [&](uint32_t g, bool out, int nch) {
-    if constexpr (fmt_is_windowed(kFmt)) {
-      // the float planar / float mono registers, placed by store_pcm_win
-      typename PcmRegs<kFmt>::type pw;
+    if constexpr (kFmt != (int)MP3G_OUT_S16) {
+      // the format's registers (replayed granules: zeros to no records, the
+      // same number of stores; zeroed in the else, as `= {}` in front of the
+      // branch comes out with other registers and another schedule)
+      typename PcmRegs<kFmt>::type pr;
       if (out) {
         f2 acc2[9];
         window_acc(acc2);
-        if constexpr (fmt_is_mono(kFmt)) pack_pcm_mono(acc2, nch, pw);
-        else pack_pcm(acc2, nch, pw);
+        pack_granule<kFmt>(acc2, nch, pr);
       } else {
 #pragma unroll
-        for (int i = 0; i < (int)(sizeof(pw) / sizeof(pw[0])); i++) pw[i] = 0.0f;
+        for (int i = 0; i < (int)(sizeof(pr) / sizeof(pr[0])); i++) pr[i] = 0;
       }
-      store_pcm_win<kFmt>(wgeom, g, out, pw, lane_fresh());
-      return;
-    } else if constexpr (fmt_is_mono(kFmt)) {
-      // one downmixed sample per lane and slot pair (replayed granules: zeros
-      // to no records, the same number of stores)
-      typename PcmRegs<kFmt>::type pm;
-      if (out) {
-        f2 acc2[9];
-        window_acc(acc2);
-        pack_pcm_mono(acc2, nch, pm);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 9; i++) pm[i] = 0;
-      }
-      store_pcm_mono(pcm, g, out, pm, lane_fresh());
-      return;
-    } else if constexpr (kFmt != (int)MP3G_OUT_S16) {
-      // float samples straight from the window's layout (replayed granules:
-      // zeros to no records, the same number of stores)
-      float pf[18];
-      if (out) {
-        f2 acc2[9];
-        window_acc(acc2);
-        pack_pcm(acc2, nch, pf);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 18; i++) pf[i] = 0.0f;
-      }
-      store_pcm_f32<kFmt>(pcm, geom, g, out, pf, lane_fresh() >> 5, lane_fresh() & 31);
+      store_granule<kFmt>(pcm, geom, wgeom, g, out, pr);
       return;
     }
+    // s16: pk lives outside the granule loop (a replayed granule stores
+    // whatever it holds to no records) and the stores are written out here
     if (out) {
       f2 acc2[9];
       window_acc(acc2);
-      // (L, R) sample pairs without LDS staging: one v_permlane32_swap per slot
-      // pair hands lane i slot 2p's (L, R) and lane 32 + i slot 2p + 1's, so
-      // every lane stores one dword per slot pair and the wave 2 x 128
-      // contiguous bytes.  Mono: the swap hands lane i channel 0's slot 2p and
-      // lane 32 + i its slot 2p + 1, stored in both halves (frame.go:671-678).
-      auto pack = [&](auto mono) {
-#pragma unroll
-        for (int p = 0; p < 9; p++) {
-          const int a = (int)__builtin_amdgcn_fmed3f(acc2[p].x, -32767.0f, 32767.0f);
-          const int b = (int)__builtin_amdgcn_fmed3f(acc2[p].y, -32767.0f, 32767.0f);
-          const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-          // low halves of (r[0], r[1]) -> one dword: L | R << 16 (R = L for mono)
-          pk[p] = __builtin_amdgcn_perm((uint32_t)(decltype(mono)::value ? r[0] : r[1]), (uint32_t)r[0], 0x05040100u);
-        }
-      };
-#if MP3G_FAST_PCM_D16
-      // (A/B) each lane stores its own channel's samples as 16-bit stores, no
-      // swap and no merge: per slot the wave writes 128 contiguous bytes; mono:
-      // the channel-0 lanes store (s, s) dwords, the others nothing
-      const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-          pcm + (size_t)g * 1152, (short)0, MP3G_PCM_BYTES_PER_GRANULE, 0x00020000);
-      if (nch == 2) {
-#pragma unroll
-        for (int p = 0; p < 9; p++) {
-          const int a = (int)__builtin_amdgcn_fmed3f(acc2[p].x, -32767.0f, 32767.0f);
-          const int b = (int)__builtin_amdgcn_fmed3f(acc2[p].y, -32767.0f, 32767.0f);
-          __builtin_amdgcn_raw_buffer_store_b16((unsigned short)a, rp, 4 * (32 * (2 * p) + k) + 2 * ch, 0, 2);
-          __builtin_amdgcn_raw_buffer_store_b16((unsigned short)b, rp, 4 * (32 * (2 * p + 1) + k) + 2 * ch, 0, 2);
-        }
-      } else {
-        const int off = ch ? kNoRecord : 0;
-#pragma unroll
-        for (int p = 0; p < 9; p++) {
-          const int a = (int)__builtin_amdgcn_fmed3f(acc2[p].x, -32767.0f, 32767.0f);
-          const int b = (int)__builtin_amdgcn_fmed3f(acc2[p].y, -32767.0f, 32767.0f);
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm((uint32_t)a, (uint32_t)a, 0x05040100u), rp,
-                                                off + 4 * (32 * (2 * p) + k), 0, 2);
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm((uint32_t)b, (uint32_t)b, 0x05040100u), rp,
-                                                off + 4 * (32 * (2 * p + 1) + k), 0, 2);
-        }
-      }
-    } else {
-      // as many stores as the output path, through a resource with no
-      // records: straight-line vmcnt accounting at the join
-      const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(pcm, (short)0, 0, 0x00020000);
-#pragma unroll
-      for (int p = 0; p < 18; p++) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)0, r0, 4 * p, 0, 2);
-    }
-#else
-      if (nch == 2) pack(std::false_type{});
-      else pack(std::true_type{});
+      pack_pcm(acc2, nch, pk);
       // stored right away: a store's data registers are free again once it
       // has issued (no s_waitcnt before their reuse on gfx950), and the loads
       // this wave waits for next were issued before these stores
@@ -1659,7 +1234,6 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       for (int p = 0; p < 9; p++)
         __builtin_amdgcn_raw_buffer_store_b32(pk[p], rp, 4 * (32 * (2 * p + hi) + k), 0, 2);  // non-temporal: c2 -1.9 %, c3 -0.8 %
     }
-#endif
   };
 
   if constexpr (kStamp) {
@@ -1687,19 +1261,9 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       else if (g == t3) __builtin_amdgcn_s_setprio(2);
     }
     const bool out = g >= out_first;
-    // the header and both channels' parameters in one LDS round trip, before
-    // anything branches on them (read under the halo test first, the header
-    // took a round trip of its own: c3 +0.7 %)
-#if MP3G_FAST_DESC_VGPR
     // header (dword 0) and the channels' first two dwords (2, 3 and 20, 21)
-    // straight from the lanes that hold them
+    // straight from the lanes that hold them, before anything branches on them
     const uint32_t h = desc_word(dv, 0);
-#else
-    const uint32_t hv = s.desc.header;
-    const uint2 cv0 = *reinterpret_cast<const uint2*>(&s.desc.ch[0]);
-    const uint2 cv1 = *reinterpret_cast<const uint2*>(&s.desc.ch[1]);
-    const uint32_t h = __builtin_amdgcn_readfirstlane(hv);
-#endif
     // does a replayed granule's V feed anything? (see v2 / DESIGN.md halo)
     bool need_v = true;
     if (!out && g + 1 < out_first) need_v = hdr_nch(gran[g + 1].header) < hdr_nch(h);
@@ -1708,17 +1272,11 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     // the channels' scalar parameters in SGPRs:
     // dword 0 = count1 | global_gain << 16 | scalefac_scale << 24,
     // dword 1 = preflag | win_switch_flag << 8 | block_type << 16 | mixed_block_flag << 24
-#if MP3G_FAST_DESC_VGPR
     const uint32_t cp0[2] = {desc_word(dv, 2), desc_word(dv, 20)};
     const uint32_t cp1[2] = {desc_word(dv, 3), desc_word(dv, 21)};
-#else
-    const uint32_t cp0[2] = {(uint32_t)__builtin_amdgcn_readfirstlane(cv0.x), (uint32_t)__builtin_amdgcn_readfirstlane(cv1.x)};
-    const uint32_t cp1[2] = {(uint32_t)__builtin_amdgcn_readfirstlane(cv0.y), (uint32_t)__builtin_amdgcn_readfirstlane(cv1.y)};
-#endif
     auto is_short = [](uint32_t d1) { return (d1 & 0x00ffff00u) == 0x00020100u; };  // win_switch 1, block_type 2
     // wave-uniform: every channel of this granule is a long block (no reorder)
     const bool all_long = !is_short(cp1[0]) && (nch == 1 || !is_short(cp1[1]));
-#if MP3G_FAST_DESC_VGPR
     // the rare paths that index scale factors per line read the descriptor
     // from the wave's LDS slot: short blocks and intensity stereo
     if (!all_long || (nch == 2 && hdr_mode(h) == 1 && (h & 0x10u))) {
@@ -1726,7 +1284,6 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       if (l < 40) reinterpret_cast<uint32_t*>(&s.desc)[l] = dv;
       wave_sync();
     }
-#endif
     // this lane's channel (lanes of an absent channel mirror channel 0's block
     // layout: no extra divergence)
     const uint32_t d0 = (act && ch) ? cp0[1] : cp0[0], d1 = (act && ch) ? cp1[1] : cp1[0];
@@ -1737,13 +1294,9 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       // long bands: lane = (ch, sfb = k), k < 22 -- the lane's own channel
       // parameters d0 / d1 (an absent channel's lanes write values nothing reads)
       const int e = lane_fresh();
-#if MP3G_FAST_DESC_VGPR
       // scalefac_l[sfb] of channel ch: descriptor byte 19 + 72 ch + sfb
       // (every lane takes part in the permute: lanes >= 22 read bytes they drop)
       const int sfl_byte = (int)desc_byte(dv, 19 + 72 * ch + (e & 31));
-#else
-      const int sfl_byte = (int)s.desc.ch[ch].scalefac_l[e & 31];
-#endif
       if ((e & 31) < 22) {
         const int sfb = e & 31;
         const int v = (int)((d0 >> 16) & 0xffu) - 210 -
@@ -1797,7 +1350,8 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       // maindata/huffman.go:130-134; mp3g_validate checks it), and requantizing
       // 0 gives 0, so long blocks need no per-line count1 test here.
       // (absent-channel lanes compute garbage that nothing reads)
-#if MP3G_FAST_P43
+      // (Every line arithmetically, the round-5 path before the table, was
+      // slower: DESIGN.md section 6, round 6.)
       const char* tb = reinterpret_cast<const char*>(&sh.p43[0]);
       uint32_t big = 0;
 #pragma unroll
@@ -1810,9 +1364,6 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
         x[2 * q] = *reinterpret_cast<const float*>(tb + (t & 0xffffu));
         x[2 * q + 1] = *reinterpret_cast<const float*>(tb + (t >> 16));
       }
-#if MP3G_P43_SCHED
-      __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
       for (int j = 0; j < 18; j++) x[j] *= gq[j >> 1];
       // (an offset at or past the table's 4 kFastP43 bytes: some |x| >= kFastP43 / 2)
@@ -1823,13 +1374,6 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
           x[2 * q + 1] = requant_gain(cw[q] >> 16, gq[q]);
         }
       }
-#else  // (A/B: every long-block line arithmetically, the round-5 path before the table)
-#pragma unroll
-      for (int q = 0; q < 9; q++) {
-        x[2 * q] = requant_gain(cw[q] & 0xffffu, gq[q]);
-        x[2 * q + 1] = requant_gain(cw[q] >> 16, gq[q]);
-      }
-#endif
     } else {
       int nsfs = 0;  // short bands whose first line lies below count1 (frame.go:229-255 loop bound)
 #pragma unroll
@@ -2083,43 +1627,21 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     // reload costs an s_waitcnt vmcnt(0), which would also wait for this
     // prefetch
     const bool more = g + 1 < end;
-#if MP3G_FAST_DESC_VGPR
     uint32_t pdw;  // the descriptor two granules ahead, one dword per lane
-#else
-    uint4 pd = {0, 0, 0, 0};
-#endif
     // issued unconditionally (straight-line vmcnt accounting, as the PCM
     // stores below): past the chunk the resources have no records
     {
-      // the next granule's descriptor is already in LDS (loaded one granule
+      // the next granule's descriptor is already here (dvn, loaded one granule
       // earlier): its count1s bound this prefetch; the descriptor two ahead
       // is loaded with it
       {
-#if MP3G_FAST_DESC_VGPR
         const uint32_t nh = desc_word(dvn, 0);
         const int c0 = (int)(desc_word(dvn, 2) & 0xffffu);
         const int c1 = (int)(desc_word(dvn, 20) & 0xffffu);
-#else
-        const uint32_t nh = __builtin_amdgcn_readfirstlane(s.descn.header);
-        const uint2 n0 = *reinterpret_cast<const uint2*>(&s.descn.ch[0]);
-        const uint2 n1 = *reinterpret_cast<const uint2*>(&s.descn.ch[1]);
-        const int c0 = (int)(__builtin_amdgcn_readfirstlane(n0.x) & 0xffffu);
-        const int c1 = (int)(__builtin_amdgcn_readfirstlane(n1.x) & 0xffffu);
-#endif
         const int lim = ch ? (hdr_nch(nh) == 2 ? c1 : 0) : c0;
         load_lines_lim(coef, g + 1, lane, cw, more ? (int)(MP3G_COEF_PER_GRANULE * sizeof(int16_t)) : 0, lim);
       }
-#if MP3G_FAST_DESC_VGPR
       pdw = load_desc_dword(gran, g + 2, lane_fresh(), g + 2 < end);
-#else
-      if (lane < 10) {
-        const bool more2 = g + 2 < end;
-        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<mp3g_granule*>(gran + g + 2), (short)0, more2 ? (int)sizeof(mp3g_granule) : 0, 0x00020000);
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rd, lane * 16, 0, 0);
-        pd = make_uint4(v[0], v[1], v[2], v[3]);
-      }
-#endif
     }
 
     // ---- matrixing (frame.go:642-648): S rows into the ring (lane (ch, sb)
@@ -2162,20 +1684,8 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     //      before the PCM stores are issued -- vmcnt counts loads and stores in
     //      issue order, so a wait for the prefetch after the stores would wait
     //      for the stores too ----
-    // (lane recomputed: the two LDS addresses kept live across the granule
-    // were spilled, and a scratch reload here waits for the PCM stores)
-#if MP3G_FAST_DESC_VGPR
     dv = dvn;
     dvn = pdw;
-#else
-    if (more) {
-      const int l = lane_fresh();
-      if (l < 10) {
-        reinterpret_cast<uint4*>(&s.desc)[l] = reinterpret_cast<const uint4*>(&s.descn)[l];
-        reinterpret_cast<uint4*>(&s.descn)[l] = pd;
-      }
-    }
-#endif
 
     window_store(g, out, nch);
     wave_sync();  // ring reads done

@@ -24,7 +24,8 @@
 // The exported vVec is rebuilt from X with 0 - x for the negated rows (the
 // reference's sums from +0 never give -0).  Tested bit-exact against the
 // oracle's PCM and state (tests/test_gpu_parity.py, exact mode).
-// (compiled in kernels_fast.hip after granule_fast.hip: shares its stages)
+// (compiled in kernels_fast.hip after granule_out.hip and granule_fast.hip:
+// shares their stages)
 #pragma clang fp contract(off)
 
 namespace mp3g {
@@ -446,13 +447,9 @@ __device__ __forceinline__ void wexact_chunk(const ChunkDesc& cd, const mp3g_gra
       f2 acc2[9];
 #pragma unroll
       for (int p = 0; p < 9; p++) acc2[p] = (f2){acc[2 * p] * 32767.0f, acc[2 * p + 1] * 32767.0f};
-      if constexpr (fmt_is_mono(kFmt)) pack_pcm_mono(acc2, P.nch, pk);
-      else pack_pcm(acc2, P.nch, pk);
+      pack_granule<kFmt>(acc2, P.nch, pk);
     }
-    if constexpr (fmt_is_windowed(kFmt)) store_pcm_win<kFmt>(wgeom, g, out, pk, lane_fresh());
-    else if constexpr (fmt_is_mono(kFmt)) store_pcm_mono(pcm, g, out, pk, lane_fresh());
-    else if constexpr (kFmt == (int)MP3G_OUT_S16) store_pcm(pcm, g, out, pk, lane_fresh() >> 5, lane_fresh() & 31);
-    else store_pcm_f32<kFmt>(pcm, geom, g, out, pk, lane_fresh() >> 5, lane_fresh() & 31);
+    store_granule<kFmt>(pcm, geom, wgeom, g, out, pk);
     wave_sync();
     // ---- history shift of the channels this granule touched: slots 18..33
     //      -> 0..15 of the 33 columns (lane (c, k): column k; k = 0 also V[16]) ----

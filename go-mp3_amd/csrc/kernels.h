@@ -153,15 +153,15 @@ hipError_t launch_fast_stamped(const ChunkDesc* d_chunks, uint32_t n_chunks, con
                                const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
                                int16_t* d_pcm, unsigned long long* d_stamps, hipStream_t stream);
 
-// The fast kernel's TU (kernels_fast.hip): its table copy, attributes and launch
-// (d_stamps = nullptr: the production build).
+// The fast kernel's TU (kernels_fast.hip): its table copy, attributes and
+// production launch (out_format: MP3G_OUT_* or kFmtWin*).
 // (req: DspTables::req, the exact requantization table of the hot-granule fallback)
 hipError_t upload_fast_tables(const FastTables& fast, const float* req);
 hipError_t fast_kernel_attributes(hipFuncAttributes* a, int* waves_per_block);
 hipError_t launch_fast(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
                        const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
-                       void* d_out, uint32_t out_format, unsigned long long* d_stamps, const ZoneScratch* zones,
-                       bool hot_stats, hipStream_t stream);
+                       void* d_out, uint32_t out_format, const ZoneScratch* zones, bool hot_stats,
+                       hipStream_t stream);
 
 // Exact mode v4 (granule_wexact.hip, same TU as the fast kernel).
 hipError_t wexact_kernel_attributes(hipFuncAttributes* a, int* waves_per_block);

@@ -133,7 +133,7 @@ hipError_t launch_granule(int variant, const ChunkDesc* d_chunks, uint32_t n_chu
                           uint32_t out_format, const ZoneScratch* zones, bool hot_stats, hipStream_t stream) {
   if (n_chunks == 0) return hipSuccess;
   if (variant == kVariantFast)
-    return launch_fast(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_out, out_format, nullptr, zones,
+    return launch_fast(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_out, out_format, zones,
                        hot_stats, stream);
   if (variant == kVariantExact4)
     return launch_wexact(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_out, out_format, stream);
@@ -143,21 +143,21 @@ hipError_t launch_granule(int variant, const ChunkDesc* d_chunks, uint32_t n_chu
   return hipGetLastError();
 }
 
-// A windowed plan's launch (kernels.h): the one-wave kernels' windowed
-// instantiations, the row table travelling in the state_out argument.
+// A windowed plan's launch (kernels.h): the plain launch in the one-wave
+// kernels' windowed instantiations (v2 has none and refuses the format),
+// without state.  The row table travels in the kernels' state_out argument --
+// a windowed plan exports no state, and an argument of its own would cost the
+// granule loops SGPRs (granule_fast.hip) -- and this cast is the only place
+// that puts it there; win_geom (granule_out.hip) takes it out again.
 hipError_t launch_granule_windows(int variant, const ChunkDesc* d_chunks, uint32_t n_chunks,
                                   const mp3g_granule* d_gran, const int16_t* d_coef, const WindowRow* d_rows,
                                   void* d_out, int win_format, const ZoneScratch* zones, bool hot_stats,
                                   hipStream_t stream) {
   if (n_chunks == 0) return hipSuccess;
   if ((win_format != kFmtWinPlanar && win_format != kFmtWinMono) || !d_rows) return hipErrorInvalidValue;
-  mp3g_state* const rows_arg = reinterpret_cast<mp3g_state*>(const_cast<WindowRow*>(d_rows));
-  if (variant == kVariantFast)
-    return launch_fast(d_chunks, n_chunks, d_gran, d_coef, nullptr, rows_arg, d_out, (uint32_t)win_format, nullptr,
-                       zones, hot_stats, stream);
-  if (variant == kVariantExact4)
-    return launch_wexact(d_chunks, n_chunks, d_gran, d_coef, nullptr, rows_arg, d_out, (uint32_t)win_format, stream);
-  return hipErrorInvalidValue;
+  return launch_granule(variant, d_chunks, n_chunks, d_gran, d_coef, nullptr,
+                        reinterpret_cast<mp3g_state*>(const_cast<WindowRow*>(d_rows)), d_out, (uint32_t)win_format,
+                        zones, hot_stats, stream);
 }
 
 }  // namespace mp3g

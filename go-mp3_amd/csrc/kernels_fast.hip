@@ -1,8 +1,9 @@
 // kernels_fast.hip -- device translation unit of the one-wave-per-chunk
 // granule kernels: fast mode v3 (granule_fast.hip, MP3G_MODE_FAST), the
 // standalone polyphase kernel (granule_synth.hip) and exact mode v4
-// (granule_wexact.hip, the default MP3G_MODE_EXACT kernel), with their own
-// copy of the fast tables.
+// (granule_wexact.hip, the default MP3G_MODE_EXACT kernel), with the PCM
+// output stage they share (granule_out.hip) and their own copy of the fast
+// tables.
 //
 // Own TU so it gets its own codegen options (Makefile): it is compiled with
 // machine LICM off.  The kernel's packed-FP32 transforms take their constants
@@ -13,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/mp3g.h"
 #include "dsp_tables.h"
@@ -28,6 +30,7 @@ __device__ float g_req[4][8207];
 }  // namespace mp3g
 
 #include "granule_hdr.h"
+#include "granule_out.hip"
 #include "granule_fast.hip"
 #include "granule_synth.hip"
 #include "granule_wexact.hip"
@@ -103,51 +106,51 @@ hipError_t launch_wexact_fmt(const ChunkDesc* d_chunks, uint32_t n_chunks, const
   return hipGetLastError();
 }
 
+// The instantiation of a runtime output format: f(the format as an integral
+// constant) for MP3G_OUT_* and for the formats of a windowed plan (kernels.h:
+// the WindowRow table then travels in d_state_out).
+template <class F>
+hipError_t with_format(uint32_t out_format, F f) {
+  switch (out_format) {
+    case MP3G_OUT_S16: return f(std::integral_constant<int, (int)MP3G_OUT_S16>{});
+    case MP3G_OUT_F32: return f(std::integral_constant<int, (int)MP3G_OUT_F32>{});
+    case MP3G_OUT_F32_PLANAR: return f(std::integral_constant<int, (int)MP3G_OUT_F32_PLANAR>{});
+    case MP3G_OUT_S16_MONO: return f(std::integral_constant<int, (int)MP3G_OUT_S16_MONO>{});
+    case MP3G_OUT_F32_MONO: return f(std::integral_constant<int, (int)MP3G_OUT_F32_MONO>{});
+    case kFmtWinPlanar: return f(std::integral_constant<int, kFmtWinPlanar>{});
+    case kFmtWinMono: return f(std::integral_constant<int, kFmtWinMono>{});
+  }
+  return hipErrorInvalidValue;
+}
+
 }  // namespace
+
+// (diagnostic: zones redone in the wave, no list; s16 only)
+hipError_t launch_fast_stamped(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
+                               const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
+                               int16_t* d_pcm, unsigned long long* d_stamps, hipStream_t stream) {
+  if (n_chunks == 0) return hipSuccess;
+  if (!d_stamps) return hipErrorInvalidValue;
+  const dim3 grid((n_chunks + v3::kWaves - 1) / v3::kWaves), block(64 * v3::kWaves);
+  hipLaunchKernelGGL(v3::granule_fast_kernel<true>, grid, block, 0, stream, d_chunks, n_chunks, d_gran, d_coef,
+                     d_state_in, d_state_out, d_pcm, static_cast<void*>(d_stamps));
+  return hipGetLastError();
+}
 
 // (the kernels take the output as int16_t* whatever the format: the float
 // instantiations cast it where they build their store resources)
 hipError_t launch_fast(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
                        const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
-                       void* d_out, uint32_t out_format, unsigned long long* d_stamps, const ZoneScratch* zones,
-                       bool hot_stats, hipStream_t stream) {
+                       void* d_out, uint32_t out_format, const ZoneScratch* zones, bool hot_stats,
+                       hipStream_t stream) {
   if (n_chunks == 0) return hipSuccess;
-  int16_t* const d_pcm = static_cast<int16_t*>(d_out);
-  if (d_stamps) {  // (diagnostic: zones in the wave, no list; s16 only)
-    if (out_format != MP3G_OUT_S16) return hipErrorInvalidValue;
-    const dim3 grid((n_chunks + v3::kWaves - 1) / v3::kWaves), block(64 * v3::kWaves);
-    hipLaunchKernelGGL(v3::granule_fast_kernel<true>, grid, block, 0, stream, d_chunks, n_chunks, d_gran, d_coef,
-                       d_state_in, d_state_out, d_pcm, static_cast<void*>(d_stamps));
-    return hipGetLastError();
-  }
-  // the production builds defer every hot zone to the plan's zone list: a
-  // fast launch without one is the diagnostic (stamped) build only
+  // the production builds defer every hot zone to the plan's zone list (only
+  // the stamped build redoes them in the wave)
   if (!zones || !zones->aux || zones->cap < (uint64_t)kZoneListPerChunk * n_chunks) return hipErrorInvalidValue;
-  switch (out_format) {
-    case MP3G_OUT_S16:
-      return launch_fast_fmt<MP3G_OUT_S16>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, zones,
-                                           hot_stats, stream);
-    case MP3G_OUT_F32:
-      return launch_fast_fmt<MP3G_OUT_F32>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, zones,
-                                           hot_stats, stream);
-    case MP3G_OUT_F32_PLANAR:
-      return launch_fast_fmt<MP3G_OUT_F32_PLANAR>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
-                                                  zones, hot_stats, stream);
-    case MP3G_OUT_S16_MONO:
-      return launch_fast_fmt<MP3G_OUT_S16_MONO>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
-                                                zones, hot_stats, stream);
-    case MP3G_OUT_F32_MONO:
-      return launch_fast_fmt<MP3G_OUT_F32_MONO>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
-                                                zones, hot_stats, stream);
-    // windowed plans (launch_granule_windows: the WindowRow table in d_state_out)
-    case kFmtWinPlanar:
-      return launch_fast_fmt<kFmtWinPlanar>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, zones,
-                                            hot_stats, stream);
-    case kFmtWinMono:
-      return launch_fast_fmt<kFmtWinMono>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, zones,
-                                          hot_stats, stream);
-  }
-  return hipErrorInvalidValue;
+  return with_format(out_format, [&](auto fmt) {
+    return launch_fast_fmt<decltype(fmt)::value>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out,
+                                                 static_cast<int16_t*>(d_out), zones, hot_stats, stream);
+  });
 }
 
 hipError_t wexact_kernel_attributes(hipFuncAttributes* a, int* waves_per_block) {
@@ -159,28 +162,10 @@ hipError_t launch_wexact(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3
                          const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
                          void* d_out, uint32_t out_format, hipStream_t stream) {
   if (n_chunks == 0) return hipSuccess;
-  int16_t* const d_pcm = static_cast<int16_t*>(d_out);
-  switch (out_format) {
-    case MP3G_OUT_S16:
-      return launch_wexact_fmt<MP3G_OUT_S16>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, stream);
-    case MP3G_OUT_F32:
-      return launch_wexact_fmt<MP3G_OUT_F32>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, stream);
-    case MP3G_OUT_F32_PLANAR:
-      return launch_wexact_fmt<MP3G_OUT_F32_PLANAR>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
-                                                    stream);
-    case MP3G_OUT_S16_MONO:
-      return launch_wexact_fmt<MP3G_OUT_S16_MONO>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
-                                                  stream);
-    case MP3G_OUT_F32_MONO:
-      return launch_wexact_fmt<MP3G_OUT_F32_MONO>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
-                                                  stream);
-    case kFmtWinPlanar:
-      return launch_wexact_fmt<kFmtWinPlanar>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm,
-                                              stream);
-    case kFmtWinMono:
-      return launch_wexact_fmt<kFmtWinMono>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, stream);
-  }
-  return hipErrorInvalidValue;
+  return with_format(out_format, [&](auto fmt) {
+    return launch_wexact_fmt<decltype(fmt)::value>(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out,
+                                                   static_cast<int16_t*>(d_out), stream);
+  });
 }
 
 hipError_t launch_synth(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran, const float* d_lines,
@@ -190,13 +175,6 @@ hipError_t launch_synth(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g
   hipLaunchKernelGGL(v3::granule_synth_kernel, grid, block, 0, stream, d_chunks, n_chunks, d_gran, d_lines, d_state_in,
                      d_state_out, d_pcm);
   return hipGetLastError();
-}
-
-hipError_t launch_fast_stamped(const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
-                               const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out,
-                               int16_t* d_pcm, unsigned long long* d_stamps, hipStream_t stream) {
-  return launch_fast(d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, MP3G_OUT_S16, d_stamps,
-                     nullptr, false, stream);
 }
 
 }  // namespace mp3g

@@ -280,15 +280,7 @@ int mp3g::plan_chunks(int device, const mp3g_stream* streams, uint32_t n_streams
   return MP3G_OK;
 }
 
-// Launch of a chunk table already on the device (d_hot: the fast kernel's
-// hot-granule counters, or null).
-int mp3g::plan_launch(uint32_t mode, const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
-                      const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out, int16_t* d_pcm,
-                      const ZoneScratch* zones, hipStream_t stream) {
-  return plan_launch_out(mode, d_chunks, n_chunks, d_gran, d_coef, d_state_in, d_state_out, d_pcm, MP3G_OUT_S16, zones,
-                         stream);
-}
-
+// Launch of a chunk table already on the device.
 int mp3g::plan_launch_out(uint32_t mode, const ChunkDesc* d_chunks, uint32_t n_chunks, const mp3g_granule* d_gran,
                           const int16_t* d_coef, const mp3g_state* d_state_in, mp3g_state* d_state_out, void* d_out,
                           uint32_t out_format, const ZoneScratch* zones, hipStream_t stream) {
@@ -316,6 +308,61 @@ struct mp3g_plan {
   WindowRow* d_rows_planar = nullptr;  // rows float [B][2][T]
   WindowRow* d_rows_mono = nullptr;    // rows float [B][T]
 };
+
+// The device side of a plan whose chunk table stands: one allocation holding
+// the chunk table, the row tables of a windowed plan (`rows`: the planar rows,
+// then the mono rows) and, in fast mode, the zone scratch (as many zones as
+// the fast kernel can record per chunk: the list never overflows).  Owns p:
+// handed out through out_plan, or deleted on error.
+static int plan_to_device(mp3g_plan* p, const std::vector<WindowRow>& rows, mp3g_plan** out_plan) {
+  DeviceGuard guard(p->device);
+  const size_t tb = (p->chunks.size() * sizeof(ChunkDesc) + 255) & ~(size_t)255;
+  const size_t rb = (rows.size() * sizeof(WindowRow) + 255) & ~(size_t)255;
+  const bool fast = plan_variant(p->mode) == kVariantFast;
+  const uint64_t zone_cap = fast ? zone_list_capacity(p->chunks.data(), p->chunks.size()) : 0u;
+  if (zone_cap > 0xffffffffu) {
+    delete p;
+    return fail(MP3G_ERR_UNSUPPORTED, "fast-mode plan of more than 2^29 chunks");
+  }
+  p->zone_cap = (uint32_t)zone_cap;
+  const size_t zb = fast ? zone_scratch_bytes(p->zone_cap) : 0;
+  hipError_t e = hipMalloc(&p->d_chunks, std::max<size_t>(tb + rb + zb, 256));
+  if (e != hipSuccess) {
+    delete p;
+    return fail(MP3G_ERR_OUT_OF_MEMORY, "hipMalloc(chunks)", e);
+  }
+  uint8_t* const b0 = reinterpret_cast<uint8_t*>(p->d_chunks);
+  if (p->windowed) {
+    p->d_rows_planar = reinterpret_cast<WindowRow*>(b0 + tb);
+    p->d_rows_mono = p->d_rows_planar + p->n_streams;
+  }
+  if (fast) p->d_zones = b0 + tb + rb;
+  if (!p->chunks.empty())
+    e = hipMemcpy(p->d_chunks, p->chunks.data(), p->chunks.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !rows.empty())
+    e = hipMemcpy(b0 + tb, rows.data(), rows.size() * sizeof(WindowRow), hipMemcpyHostToDevice);
+  if (e == hipSuccess && fast) e = zone_scratch_init(p->d_zones, p->zone_cap);
+  if (e != hipSuccess) {
+    (void)hipFree(p->d_chunks);
+    delete p;
+    return fail(MP3G_ERR_DEVICE, "hipMemcpy(chunks)", e);
+  }
+  *out_plan = p;
+  return MP3G_OK;
+}
+
+// What the launches of a stateful plan share: the plan's device made current
+// (the caller's is restored on return), every chunk that exports state given
+// somewhere to export it, then `launch`.
+template <class F>
+static int launch_on_plan_device(const mp3g_plan* p, const mp3g_state* d_state_out, F launch) {
+  DeviceGuard guard(p->device);
+  if (guard.err != hipSuccess) return fail(MP3G_ERR_NO_DEVICE, "hipSetDevice", guard.err);
+  for (const ChunkDesc& c : p->chunks) {
+    if ((c.flags & kChunkStateOut) && !d_state_out) return fail(MP3G_ERR_INVALID_ARGUMENT, "state_out needed");
+  }
+  return launch();
+}
 
 extern "C" {
 
@@ -410,34 +457,7 @@ int mp3g_plan_create(int device, const mp3g_stream* streams, uint32_t n_streams,
   p->device = device;
   p->mode = mode;
   p->n_streams = n_streams;
-  DeviceGuard guard(device);
-  // the chunk table, then the zone scratch (as many zones as the fast kernel
-  // can record per chunk: the list never overflows)
-  const size_t tb = (p->chunks.size() * sizeof(ChunkDesc) + 255) & ~(size_t)255;
-  const bool fast = plan_variant(mode) == kVariantFast;
-  const uint64_t zone_cap = fast ? zone_list_capacity(p->chunks.data(), p->chunks.size()) : 0u;
-  if (zone_cap > 0xffffffffu) {
-    delete p;
-    return fail(MP3G_ERR_UNSUPPORTED, "fast-mode plan of more than 2^29 chunks");
-  }
-  p->zone_cap = (uint32_t)zone_cap;
-  const size_t zb = fast ? zone_scratch_bytes(p->zone_cap) : 0;
-  hipError_t e = hipMalloc(&p->d_chunks, std::max<size_t>(tb + zb, 256));
-  if (e != hipSuccess) {
-    delete p;
-    return fail(MP3G_ERR_OUT_OF_MEMORY, "hipMalloc(chunks)", e);
-  }
-  if (fast) p->d_zones = reinterpret_cast<uint8_t*>(p->d_chunks) + tb;
-  if (!p->chunks.empty()) e = hipMemcpy(p->d_chunks, p->chunks.data(), p->chunks.size() * sizeof(ChunkDesc),
-                                        hipMemcpyHostToDevice);
-  if (e == hipSuccess && fast) e = zone_scratch_init(p->d_zones, p->zone_cap);
-  if (e != hipSuccess) {
-    (void)hipFree(p->d_chunks);
-    delete p;
-    return fail(MP3G_ERR_DEVICE, "hipMemcpy(chunks)", e);
-  }
-  *out_plan = p;
-  return MP3G_OK;
+  return plan_to_device(p, {}, out_plan);
 }
 
 int mp3g_plan_destroy(mp3g_plan* p) {
@@ -491,14 +511,11 @@ int mp3g_plan_execute_out(mp3g_plan* p, const mp3g_granule* d_gran, const int16_
   }
   if (p->chunks.empty()) return MP3G_OK;
   if (!d_gran || !d_coef || !d_pcm) return fail(MP3G_ERR_INVALID_ARGUMENT, "null device buffer");
-  DeviceGuard guard(p->device);
-  if (guard.err != hipSuccess) return fail(MP3G_ERR_NO_DEVICE, "hipSetDevice", guard.err);
-  for (const ChunkDesc& c : p->chunks) {
-    if ((c.flags & kChunkStateOut) && !d_state_out) return fail(MP3G_ERR_INVALID_ARGUMENT, "state_out needed");
-  }
-  const ZoneScratch zs{static_cast<uint32_t*>(p->d_zones), p->zone_cap};
-  return plan_launch_out(p->mode, p->d_chunks, (uint32_t)p->chunks.size(), d_gran, d_coef, d_state_in, d_state_out,
-                         d_pcm, out_format, p->d_zones ? &zs : nullptr, static_cast<hipStream_t>(hip_stream));
+  return launch_on_plan_device(p, d_state_out, [&] {
+    const ZoneScratch zs{static_cast<uint32_t*>(p->d_zones), p->zone_cap};
+    return plan_launch_out(p->mode, p->d_chunks, (uint32_t)p->chunks.size(), d_gran, d_coef, d_state_in, d_state_out,
+                           d_pcm, out_format, p->d_zones ? &zs : nullptr, static_cast<hipStream_t>(hip_stream));
+  });
 }
 
 // Windowed plans (include/mp3g.h).  The chunk table is that of the streams
@@ -555,39 +572,7 @@ int mp3g_plan_create_windows(int device, const mp3g_stream* streams, const mp3g_
   p->n_streams = n_streams;
   p->windowed = true;
   p->win_T = T;
-  DeviceGuard guard(device);
-  // the chunk table, the two row tables, then the zone scratch (as mp3g_plan_create)
-  const size_t tb = (p->chunks.size() * sizeof(ChunkDesc) + 255) & ~(size_t)255;
-  const size_t rb = (tab.size() * sizeof(WindowRow) + 255) & ~(size_t)255;
-  const bool fast = plan_variant(mode) == kVariantFast;
-  const uint64_t zone_cap = fast ? zone_list_capacity(p->chunks.data(), p->chunks.size()) : 0u;
-  if (zone_cap > 0xffffffffu) {
-    delete p;
-    return fail(MP3G_ERR_UNSUPPORTED, "fast-mode plan of more than 2^29 chunks");
-  }
-  p->zone_cap = (uint32_t)zone_cap;
-  const size_t zb = fast ? zone_scratch_bytes(p->zone_cap) : 0;
-  hipError_t e = hipMalloc(&p->d_chunks, std::max<size_t>(tb + rb + zb, 256));
-  if (e != hipSuccess) {
-    delete p;
-    return fail(MP3G_ERR_OUT_OF_MEMORY, "hipMalloc(chunks)", e);
-  }
-  uint8_t* const b0 = reinterpret_cast<uint8_t*>(p->d_chunks);
-  p->d_rows_planar = reinterpret_cast<WindowRow*>(b0 + tb);
-  p->d_rows_mono = p->d_rows_planar + n_streams;
-  if (fast) p->d_zones = b0 + tb + rb;
-  if (!p->chunks.empty())
-    e = hipMemcpy(p->d_chunks, p->chunks.data(), p->chunks.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice);
-  if (e == hipSuccess && !tab.empty())
-    e = hipMemcpy(p->d_rows_planar, tab.data(), tab.size() * sizeof(WindowRow), hipMemcpyHostToDevice);
-  if (e == hipSuccess && fast) e = zone_scratch_init(p->d_zones, p->zone_cap);
-  if (e != hipSuccess) {
-    (void)hipFree(p->d_chunks);
-    delete p;
-    return fail(MP3G_ERR_DEVICE, "hipMemcpy(chunks)", e);
-  }
-  *out_plan = p;
-  return MP3G_OK;
+  return plan_to_device(p, tab, out_plan);
 }
 
 int mp3g_plan_execute_windows(mp3g_plan* p, const mp3g_granule* d_gran, const int16_t* d_coef, void* d_out,
@@ -635,14 +620,11 @@ int mp3g_plan_synth_execute(mp3g_plan* p, const mp3g_granule* d_gran, const floa
   if (p->windowed) return fail(MP3G_ERR_INVALID_ARGUMENT, "a windowed plan runs with mp3g_plan_execute_windows");
   if (p->chunks.empty()) return MP3G_OK;
   if (!d_gran || !d_lines || !d_pcm) return fail(MP3G_ERR_INVALID_ARGUMENT, "null device buffer");
-  DeviceGuard guard(p->device);
-  if (guard.err != hipSuccess) return fail(MP3G_ERR_NO_DEVICE, "hipSetDevice", guard.err);
-  for (const ChunkDesc& c : p->chunks) {
-    if ((c.flags & kChunkStateOut) && !d_state_out) return fail(MP3G_ERR_INVALID_ARGUMENT, "state_out needed");
-  }
-  HIP_TRY(launch_synth(p->d_chunks, (uint32_t)p->chunks.size(), d_gran, d_lines, d_state_in, d_state_out, d_pcm,
-                       static_cast<hipStream_t>(hip_stream)));
-  return MP3G_OK;
+  return launch_on_plan_device(p, d_state_out, [&] {
+    HIP_TRY(launch_synth(p->d_chunks, (uint32_t)p->chunks.size(), d_gran, d_lines, d_state_in, d_state_out, d_pcm,
+                         static_cast<hipStream_t>(hip_stream)));
+    return (int)MP3G_OK;
+  });
 }
 
 int mp3g_huffman_execute(int device, const mp3g_hjob* d_jobs, uint64_t n_granules, const uint8_t* d_md,

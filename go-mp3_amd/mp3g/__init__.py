@@ -330,18 +330,28 @@ def scan_streams(datas, n_threads=0):
     h = C.c_void_p()
     t0 = time.perf_counter()
     _check(lib().mp3g_scan_streams(len(datas), ptrs, lens, n_threads, C.byref(h)))
-    scan_s = time.perf_counter() - t0
+    return _scan_result(h, len(datas), time.perf_counter() - t0)
+
+
+def _scan_result(h, n_streams, scan_s, rows=False):
+    """The buffers of scan handle h as numpy copies (scan_streams' dict; rows:
+    a windowed scan's "rows" with them), and the handle freed."""
     try:
         ng, nmd = C.c_uint64(), C.c_uint64()
-        pg, pj, pm, ps, pst = (C.c_void_p() for _ in range(5))
+        pg, pj, pm, ps, pst, pr = (C.c_void_p() for _ in range(6))
         _check(lib().mp3g_scan_buffers(h, C.byref(ng), C.byref(nmd), C.byref(pg), C.byref(pj), C.byref(pm),
                                        C.byref(ps), C.byref(pst)))
         n = ng.value
-        return {"granules": _copy_out(pg, n * GRANULE_DTYPE.itemsize, GRANULE_DTYPE),
-                "jobs": _copy_out(pj, 2 * n * HJOB_DTYPE.itemsize, HJOB_DTYPE),
-                "main_data": _copy_out(pm, nmd.value, np.uint8),
-                "streams": _copy_out(ps, len(datas) * STREAM_DTYPE.itemsize, STREAM_DTYPE),
-                "end_status": _copy_out(pst, len(datas) * 4, np.int32), "scan_s": scan_s}
+        s = {"granules": _copy_out(pg, n * GRANULE_DTYPE.itemsize, GRANULE_DTYPE),
+             "jobs": _copy_out(pj, 2 * n * HJOB_DTYPE.itemsize, HJOB_DTYPE),
+             "main_data": _copy_out(pm, nmd.value, np.uint8),
+             "streams": _copy_out(ps, n_streams * STREAM_DTYPE.itemsize, STREAM_DTYPE),
+             "end_status": _copy_out(pst, n_streams * 4, np.int32)}
+        if rows:
+            _check(lib().mp3g_scan_window_rows(h, C.byref(pr)))
+            s["rows"] = _copy_out(pr, n_streams * WINDOW_ROW_DTYPE.itemsize, WINDOW_ROW_DTYPE)
+        s["scan_s"] = scan_s
+        return s
     finally:
         lib().mp3g_scan_free(h)
 
@@ -482,6 +492,34 @@ def decode_streams(datas, mode=MODE_EXACT, n_threads=0, device=0):
     return _take(pcm, k, np.int16, (k, 576, 2)), streams, status[:len(datas)]
 
 
+def _decode_scan(s, make_plan, d_out, out_format, mode, device, then=None):
+    """The device side of the *_tensor calls, on the current torch stream: the
+    scan's granules, jobs and main data uploaded, the main-data kernel into
+    torch-owned coefficient rows, then the plan (make_plan()) into d_out and
+    then(stream), if given.  Returns when the kernels are done (the plan and the
+    input buffers, which the kernels read, are released then).  A scan without
+    granules launches nothing."""
+    import torch
+    n = len(s["granules"])
+    if not n:
+        return
+    dev = torch.device("cuda", device)
+    d_g = torch.from_numpy(s["granules"].view(np.uint8)).to(dev)
+    d_j = torch.from_numpy(s["jobs"].view(np.uint8)).to(dev)
+    d_m = torch.from_numpy(s["main_data"]).to(dev)
+    d_c = torch.empty(n * 1152, dtype=torch.int16, device=dev)
+    plan = make_plan()
+    st = torch.cuda.current_stream(dev)
+    # (rows to count1: the one-wave plan kernels read no further)
+    flags = (0 if mode & FLAG_KERNEL_V2 else HUFF_ROWS_COUNT1) | huffman_stage_flags(s["jobs"], n)
+    huffman_execute(d_j, n, d_m, d_g, d_c, stream=st.cuda_stream, device=device, flags=flags)
+    plan.execute(d_g, d_c, d_out, stream=st.cuda_stream, out_format=out_format)
+    if then is not None:
+        then(st)
+    st.synchronize()
+    plan.close()
+
+
 def decode_streams_tensor(datas, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, n_threads=0, device=0):
     """Bitstreams in, one device tensor out: the host scan, one upload, then the
     main-data kernel and the plan kernel on torch-owned buffers and the
@@ -504,21 +542,7 @@ def decode_streams_tensor(datas, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, n_t
     dev = torch.device("cuda", device)
     per = 576 if out_format in _OUT_MONO else 1152  # samples per granule slot
     out = torch.empty(n * per, dtype=torch.int16 if out_format in _OUT_INT16 else torch.float32, device=dev)
-    if n:
-        d_g = torch.from_numpy(s["granules"].view(np.uint8)).to(dev)
-        d_j = torch.from_numpy(s["jobs"].view(np.uint8)).to(dev)
-        d_m = torch.from_numpy(s["main_data"]).to(dev)
-        d_c = torch.empty(n * 1152, dtype=torch.int16, device=dev)
-        plan = Plan(streams, mode=mode, device=device)
-        st = torch.cuda.current_stream(dev)
-        # (rows to count1: the one-wave plan kernels read no further)
-        flags = (0 if mode & FLAG_KERNEL_V2 else HUFF_ROWS_COUNT1) | huffman_stage_flags(s["jobs"], n)
-        huffman_execute(d_j, n, d_m, d_g, d_c, stream=st.cuda_stream, device=device, flags=flags)
-        plan.execute(d_g, d_c, out, stream=st.cuda_stream, out_format=out_format)
-        # the inputs and the plan's chunk table are read by the kernels: they
-        # are released once the stream is done with them
-        st.synchronize()
-        plan.close()
+    _decode_scan(s, lambda: Plan(streams, mode=mode, device=device), out, out_format, mode, device)
     if out_format == OUT_F32_PLANAR:
         views = planar_views(out, streams)
     elif out_format in _OUT_MONO:
@@ -537,38 +561,22 @@ def scan_windows(datas, starts, n_samples, gapless=False, n_threads=0):
     [WINDOW_ROW_DTYPE]: lead (granules decoded with PCM off), skip (samples of
     the window's first granule in front of it) and n_valid (samples the row
     receives).  gapless: a bool, or one per stream."""
-    win = np.zeros(max(1, len(datas)), WINDOW_DTYPE)
-    win["start"][:len(datas)] = np.asarray(starts, dtype=np.uint64)
-    win["n_samples"] = int(n_samples)
-    win["flags"][:len(datas)] = np.where(np.broadcast_to(np.asarray(gapless, dtype=bool), (len(datas),)),
-                                         WINDOW_GAPLESS, 0)
-    return _scan_windows(datas, win, n_threads)
+    return _scan_windows(datas, starts, int(n_samples), gapless, n_threads)
 
 
-def _scan_windows(datas, win, n_threads=0):
-    """scan_windows on a window table [WINDOW_DTYPE] (mp3g_scan_windows takes a
-    length per stream; scan_windows gives every stream the same)."""
+def _scan_windows(datas, starts, lengths, gapless, n_threads=0):
+    """scan_windows with a window length per stream (or one for all), as
+    mp3g_scan_windows takes them."""
+    B = len(datas)
+    win = np.zeros(max(1, B), WINDOW_DTYPE)
+    win["start"][:B] = np.asarray(starts, dtype=np.uint64)
+    win["n_samples"][:B] = lengths
+    win["flags"][:B] = np.where(np.broadcast_to(np.asarray(gapless, dtype=bool), (B,)), WINDOW_GAPLESS, 0)
     bufs, ptrs, lens = _stream_args(datas)
     h = C.c_void_p()
     t0 = time.perf_counter()
-    _check(lib().mp3g_scan_windows(len(datas), ptrs, lens, _ptr(win), n_threads, C.byref(h)))
-    scan_s = time.perf_counter() - t0
-    try:
-        ng, nmd = C.c_uint64(), C.c_uint64()
-        pg, pj, pm, ps, pst, pr = (C.c_void_p() for _ in range(6))
-        _check(lib().mp3g_scan_buffers(h, C.byref(ng), C.byref(nmd), C.byref(pg), C.byref(pj), C.byref(pm),
-                                       C.byref(ps), C.byref(pst)))
-        _check(lib().mp3g_scan_window_rows(h, C.byref(pr)))
-        n = ng.value
-        return {"granules": _copy_out(pg, n * GRANULE_DTYPE.itemsize, GRANULE_DTYPE),
-                "jobs": _copy_out(pj, 2 * n * HJOB_DTYPE.itemsize, HJOB_DTYPE),
-                "main_data": _copy_out(pm, nmd.value, np.uint8),
-                "streams": _copy_out(ps, len(datas) * STREAM_DTYPE.itemsize, STREAM_DTYPE),
-                "end_status": _copy_out(pst, len(datas) * 4, np.int32),
-                "rows": _copy_out(pr, len(datas) * WINDOW_ROW_DTYPE.itemsize, WINDOW_ROW_DTYPE),
-                "scan_s": scan_s}
-    finally:
-        lib().mp3g_scan_free(h)
+    _check(lib().mp3g_scan_windows(B, ptrs, lens, _ptr(win), n_threads, C.byref(h)))
+    return _scan_result(h, B, time.perf_counter() - t0, rows=True)
 
 
 def decode_windows_tensor(datas, starts, n_samples, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, gapless=False,
@@ -590,21 +598,11 @@ def decode_windows_tensor(datas, starts, n_samples, mode=MODE_EXACT, out_format=
     if out_format not in (OUT_F32_PLANAR, OUT_F32_MONO):
         raise Mp3gError(8 if out_bytes_per_granule(out_format) else 1, "windowed output is OUT_F32_PLANAR or OUT_F32_MONO")
     s = scan_windows(datas, starts, n_samples, gapless=gapless, n_threads=n_threads)
-    n, B, T = len(s["granules"]), len(datas), int(n_samples)
+    B, T = len(datas), int(n_samples)
     dev = torch.device("cuda", device)
     batch = torch.zeros((B, 2, T) if out_format == OUT_F32_PLANAR else (B, T), dtype=torch.float32, device=dev)
-    if n:
-        d_g = torch.from_numpy(s["granules"].view(np.uint8)).to(dev)
-        d_j = torch.from_numpy(s["jobs"].view(np.uint8)).to(dev)
-        d_m = torch.from_numpy(s["main_data"]).to(dev)
-        d_c = torch.empty(n * 1152, dtype=torch.int16, device=dev)
-        plan = WindowPlan(s["streams"], s["rows"], T, mode=mode, device=device)
-        st = torch.cuda.current_stream(dev)
-        flags = HUFF_ROWS_COUNT1 | huffman_stage_flags(s["jobs"], n)
-        huffman_execute(d_j, n, d_m, d_g, d_c, stream=st.cuda_stream, device=device, flags=flags)
-        plan.execute(d_g, d_c, batch, stream=st.cuda_stream, out_format=out_format)
-        st.synchronize()
-        plan.close()
+    _decode_scan(s, lambda: WindowPlan(s["streams"], s["rows"], T, mode=mode, device=device), batch, out_format, mode,
+                 device)
     return batch, s["rows"]["n_valid"].astype(np.int64), s["end_status"]
 
 
@@ -755,33 +753,26 @@ def decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=MODE_EX
     planar = out_format == OUT_F32_PLANAR
     batch = torch.zeros((B, 2, T) if planar else (B, T), dtype=torch.float32, device=dev)
     lengths = np.zeros(B, np.int64)
-    win = np.zeros(max(1, B), WINDOW_DTYPE)
-    win["flags"][:B] = np.where(np.broadcast_to(np.asarray(gapless, dtype=bool), (B,)), WINDOW_GAPLESS, 0)
+    # each stream's source window [src0, src0 + src_n) (none: no valid frame)
+    src0, src_n = np.zeros(B, np.uint64), np.zeros(B, np.uint64)
     for k in range(B):
         if rates[k] and T:
             a, b = rs[int(rates[k])].src_window(starts[k], T)
             if b - a > (1 << 26):
                 raise Mp3gError(1, "source window of more than MP3G_WINDOW_MAX_SAMPLES samples")
-            win["start"][k], win["n_samples"][k] = a, b - a
-    s = _scan_windows(datas, win, n_threads)
-    n, T_src = len(s["granules"]), int(win["n_samples"].max())
-    if n:
-        d_g = torch.from_numpy(s["granules"].view(np.uint8)).to(dev)
-        d_j = torch.from_numpy(s["jobs"].view(np.uint8)).to(dev)
-        d_m = torch.from_numpy(s["main_data"]).to(dev)
-        d_c = torch.empty(n * 1152, dtype=torch.int16, device=dev)
-        inter = torch.zeros((B, 2, T_src) if planar else (B, T_src), dtype=torch.float32, device=dev)
-        plan = WindowPlan(s["streams"], s["rows"], T_src, mode=mode, device=device)
-        st = torch.cuda.current_stream(dev)
-        flags = HUFF_ROWS_COUNT1 | huffman_stage_flags(s["jobs"], n)
-        huffman_execute(d_j, n, d_m, d_g, d_c, stream=st.cuda_stream, device=device, flags=flags)
-        plan.execute(d_g, d_c, inter, stream=st.cuda_stream, out_format=out_format)
+            src0[k], src_n[k] = a, b - a
+    s = _scan_windows(datas, src0, src_n, gapless, n_threads)
+    T_src = int(src_n.max()) if B else 0
+    inter = (torch.zeros((B, 2, T_src) if planar else (B, T_src), dtype=torch.float32, device=dev)
+             if len(s["granules"]) else None)
+
+    def resample(st):  # one launch per source rate, behind the windowed decode
         n_valid = s["rows"]["n_valid"].astype(np.int64)
         for f, r in rs.items():
             ks = [k for k in range(B) if rates[k] == f and n_valid[k] > 0]
             rows = np.zeros(len(ks), RESAMPLE_ROW_DTYPE)
             for i, k in enumerate(ks):
-                a, want = int(win["start"][k]), int(win["n_samples"][k])
+                a, want = int(src0[k]), int(src_n[k])
                 # fewer samples than asked for: the stream ends at N = a + n_valid
                 ln = T if n_valid[k] >= want else min(T, max(0, r.out_len(a + int(n_valid[k])) - starts[k]))
                 lengths[k] = ln
@@ -789,8 +780,9 @@ def decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=MODE_EX
             rows = rows[rows["n_out"] > 0]
             if len(rows):
                 r.rows(inter, batch, rows, stream=st.cuda_stream)
-        st.synchronize()
-        plan.close()
+
+    _decode_scan(s, lambda: WindowPlan(s["streams"], s["rows"], T_src, mode=mode, device=device), inter, out_format,
+                 mode, device, then=resample)
     for r in rs.values():
         r.close()
     return batch, lengths, s["end_status"], rates

@@ -112,7 +112,7 @@ def main():
             lo, hi = rs["best"].src_window(int(starts[k]), T)
             win["start"][k], win["n_samples"][k] = lo, hi - lo
         T_src = int(win["n_samples"].max())
-        s = mp3g._scan_windows(datas, win, 16)
+        s = mp3g._scan_windows(datas, win["start"], win["n_samples"], False, 16)
         n = len(s["granules"])
         d_g = torch.from_numpy(s["granules"].view(np.uint8)).to(dev)
         d_j = torch.from_numpy(s["jobs"].view(np.uint8)).to(dev)
