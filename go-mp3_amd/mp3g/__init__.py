@@ -145,6 +145,18 @@ def lib():
             L.mp3g_resample_host.argtypes = [vp, vp, u64, u64, u64, u64, vp]
             L.mp3g_resample_rows.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp]
             L.mp3g_stream_rates.argtypes = [u32, vp, vp, C.c_int, vp, vp]
+        if hasattr(L, "mp3g_logmel_create"):  # (an older build through MP3G_LIB: A/B runs)
+            L.mp3g_logmel_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, u32,
+                                             C.POINTER(vp)]
+            L.mp3g_logmel_free.argtypes = [vp]
+            L.mp3g_logmel_free.restype = None
+            L.mp3g_logmel_info.argtypes = [vp, C.POINTER(u32)] + [C.POINTER(vp)] * 4 + [C.POINTER(u32)]
+            L.mp3g_logmel_frames.argtypes = [vp, u64]
+            L.mp3g_logmel_frames.restype = u64
+            L.mp3g_logmel_host.argtypes = [vp, vp, u64, u64, vp, u64]
+            L.mp3g_logmel_execute.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
+            L.mp3g_logmel_log10f.argtypes = [vp, u64, vp]
+            L.mp3g_logmel_log10f.restype = None
         L.mp3g_lame_parse.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo)]
         L.mp3g_lame_parse_reader.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo), C.POINTER(C.c_size_t)]
         L.mp3g_lame_total_delay.argtypes = [C.POINTER(_LameInfo)]
@@ -786,6 +798,138 @@ def decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=MODE_EX
     for r in rs.values():
         r.close()
     return batch, lengths, s["end_status"], rates
+
+
+# ---- log-mel features of decoded rows (include/mp3g.h) ----------------------
+LOGMEL_CENTER = 1
+LOGMEL_CLAMP = 2
+
+
+def log10f(x):
+    """mp3g_log10f of every element of x (float32; normal, positive, finite):
+    the features' logarithm, for tests."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.empty_like(x)
+    lib().mp3g_logmel_log10f(_ptr(x), x.size, _ptr(y))
+    return y
+
+
+class LogMel:
+    """Log-mel features of float32 rows (mp3g_logmel_*): a Hann-windowed STFT
+    power spectrum by direct DFT, Slaney's mel filter bank, log10 of the power
+    floored at 1e-10 and, with clamp, Whisper's (max(y, max y - 8) + 4) / 4.
+    Every sum is ONE float32 FMA chain in ascending order, so the device call
+    (execute) equals the host reference (host) bit for bit.  device=None (or
+    -1) makes a host-only object; fmax=0 means rate / 2."""
+
+    def __init__(self, rate=16000, n_fft=400, hop=160, n_mels=80, fmin=0.0, fmax=0.0, center=True, clamp=True,
+                 device=None):
+        self._h = C.c_void_p()
+        self.device = -1 if device is None else int(device)
+        self.rate, self.n_fft, self.hop, self.n_mels = int(rate), int(n_fft), int(hop), int(n_mels)
+        self.center, self.clamp = bool(center), bool(clamp)
+        self.flags = (LOGMEL_CENTER if center else 0) | (LOGMEL_CLAMP if clamp else 0)
+        _check(lib().mp3g_logmel_create(self.device, self.rate, self.n_fft, self.hop, self.n_mels, float(fmin),
+                                        float(fmax), self.flags, C.byref(self._h)))
+        k, t = C.c_uint32(), C.c_uint32()
+        p = [C.c_void_p() for _ in range(4)]
+        _check(lib().mp3g_logmel_info(self._h, C.byref(k), *[C.byref(q) for q in p], C.byref(t)))
+        self.K, self.tile_frames = k.value, t.value
+        self.pad = self.n_fft // 2 if center else 0
+
+        def view(q, ctype, shape):  # a view of the library's table: valid while this object lives
+            return np.ctypeslib.as_array(C.cast(q, C.POINTER(ctype)), shape=shape)
+        self.cw = view(p[0], C.c_float, (self.K, self.n_fft))
+        self.sw = view(p[1], C.c_float, (self.K, self.n_fft))
+        self.wm = view(p[2], C.c_float, (self.n_mels, self.K))
+        self.support = view(p[3], C.c_uint32, (self.n_mels, 2))
+
+    def frames(self, T):
+        """The frames a row of T samples has (mp3g_logmel_frames)."""
+        return int(lib().mp3g_logmel_frames(self._h, int(T)))
+
+    def host(self, x, n_frames=None, frame_stride=None):
+        """The reference on the CPU (mp3g_logmel_host): features [n_mels,
+        n_frames] of the float32 row x (n_frames: all by default); with a
+        frame_stride the full [n_mels, frame_stride] buffer, zeros where
+        nothing is written."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = self.frames(len(x)) if n_frames is None else int(n_frames)
+        stride = n if frame_stride is None else int(frame_stride)
+        out = np.zeros((self.n_mels, max(stride, 0)), np.float32)
+        _check(lib().mp3g_logmel_host(self._h, _ptr(x) if len(x) else None, len(x), n, _ptr(out) if out.size else None,
+                                      stride))
+        return out
+
+    def execute(self, d_src, d_out=None, n_frames=None, stream=None):
+        """The device call (mp3g_logmel_execute): d_src float32 [B, C, T] (C = 1
+        or 2) or [B, T], contiguous on this object's device; d_out float32
+        [B, C, n_mels, S] or [B, n_mels, S] with S >= n_frames (made here when
+        None: S = n_frames, all frames by default).  Writes the n_frames
+        features of each mel row, nothing else.  Asynchronous on `stream` (a
+        hipStream_t; None = the current torch stream).  Returns d_out."""
+        import torch
+        if d_src.dtype != torch.float32 or not d_src.is_contiguous() or d_src.dim() not in (2, 3) or not d_src.is_cuda:
+            raise ValueError("LogMel.execute: a contiguous float32 device tensor [B, C, T] or [B, T]")
+        B, T = int(d_src.shape[0]), int(d_src.shape[-1])
+        planes = int(d_src.shape[1]) if d_src.dim() == 3 else 1
+        n = self.frames(T) if n_frames is None else int(n_frames)
+        lead = (B, planes) if d_src.dim() == 3 else (B,)
+        if d_out is None:
+            d_out = torch.empty(lead + (self.n_mels, n), dtype=torch.float32, device=d_src.device)
+        if (d_out.dtype != torch.float32 or not d_out.is_contiguous() or not d_out.is_cuda
+                or tuple(d_out.shape[:-1]) != lead + (self.n_mels,)):
+            raise ValueError("LogMel.execute: d_out is a contiguous float32 device tensor [B, (C,) n_mels, S]")
+        if stream is None:
+            stream = torch.cuda.current_stream(d_src.device).cuda_stream
+        _check(lib().mp3g_logmel_execute(self._h, C.c_void_p(d_src.data_ptr()) if d_src.numel() else None, B, planes, T,
+                                         C.c_void_p(d_out.data_ptr()) if d_out.numel() else None, n,
+                                         int(d_out.shape[-1]), C.c_void_p(stream) if stream else None))
+        return d_out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.cw = self.sw = self.wm = self.support = None
+            lib().mp3g_logmel_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def decode_windows_logmel_tensor(datas, starts, n_samples, rate=16000, n_fft=400, hop=160, n_mels=80, clamp=True,
+                                 center=True, fmin=0.0, fmax=0.0, n_frames=None, mode=MODE_EXACT,
+                                 out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0, device=0):
+    """decode_windows_resampled_tensor followed by LogMel.execute on the same
+    torch stream: the log-mel features of each stream's window [starts[k],
+    starts[k] + n_samples) at `rate`, zero padding included.  F = n_frames, by
+    default n_samples // hop with center (Whisper's count, which drops the last
+    frame) and every frame without.
+
+    Returns (features, frame_lengths, end_status, rates): features [B, n_mels,
+    F] (OUT_F32_MONO) or [B, 2, n_mels, F] (OUT_F32_PLANAR) on cuda:device,
+    equal to LogMel.host on the rows of decode_windows_resampled_tensor bit for
+    bit; frame_lengths int64[B] = min(F, ceil(lengths / hop)), the frames that
+    start inside each stream's valid samples."""
+    import torch
+    lm = LogMel(rate, n_fft, hop, n_mels, fmin, fmax, center=center, clamp=clamp, device=device)
+    try:
+        T = int(n_samples)
+        avail = lm.frames(T)
+        F = (min(avail, T // lm.hop) if center else avail) if n_frames is None else int(n_frames)
+        if F < 0 or F > avail:
+            raise Mp3gError(1, "more frames than a row of n_samples has")
+        batch, lengths, end_status, rates = decode_windows_resampled_tensor(
+            datas, starts, T, rate, mode=mode, out_format=out_format, gapless=gapless, quality=quality,
+            n_threads=n_threads, device=device)
+        feats = lm.execute(batch, n_frames=F)
+        torch.cuda.current_stream(feats.device).synchronize()
+    finally:
+        lm.close()
+    return feats, np.minimum(F, -(-lengths // lm.hop)), end_status, rates
 
 
 def _host_buffer(out, want_int16, want_float32=False):

@@ -53,7 +53,7 @@ extern "C" {
  *    mp3g_scan_windows, mp3g_scan_window_rows, mp3g_plan_create_windows and
  *    mp3g_plan_execute_windows; sample-rate conversion of decoded rows --
  *    mp3g_resampler_*, mp3g_resample_host, mp3g_resample_rows and
- *    mp3g_stream_rates.) */
+ *    mp3g_stream_rates; log-mel features of decoded rows -- mp3g_logmel_*.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -617,6 +617,86 @@ int mp3g_resample_rows(const mp3g_resampler* r, const float* d_src, uint32_t src
  * stream without a valid frame gets 0 and 0. */
 int mp3g_stream_rates(uint32_t n_streams, const uint8_t* const* datas, const size_t* lens, int n_threads,
                       int* rates, int* channels);
+
+/* ---- log-mel features of decoded rows ---------------------------------------
+ * The input of a speech model from the float rows of the windowed, resampled
+ * decode: STFT power, mel filter bank, log10 and (MP3G_LOGMEL_CLAMP) Whisper's
+ * dynamic-range normalisation.  Every feature is a fixed sequence of float32
+ * operations, so the device call equals mp3g_logmel_host bit for bit.  No
+ * reference counterpart (go-mp3 delivers samples).
+ *
+ * Parameters.  n_fft a multiple of 4 in [16, 1024], 1 <= hop <= n_fft, n_mels
+ * in 1..128, rate > 0, 0 <= fmin < fmax <= rate / 2 (fmax = 0 means rate / 2);
+ * K = n_fft / 2 + 1 bins.  A value that is not positive, an unknown flag, hop >
+ * n_fft or an fmin / fmax outside those relations is MP3G_ERR_INVALID_ARGUMENT;
+ * an n_fft or n_mels outside the supported range MP3G_ERR_UNSUPPORTED; both
+ * before any device call, with *out = NULL.
+ *
+ * Framing.  One row is a float32 signal x[0, T) (a plane of the dense batch,
+ * its zero padding included).  With MP3G_LOGMEL_CENTER pad = n_fft / 2 and
+ * frame f reads xr[f hop - pad + n], n = 0 .. n_fft - 1, where xr is x
+ * reflected about both ends (xr[-i] = x[i], xr[T - 1 + i] = x[T - 1 - i]:
+ * torch.stft(center=True, pad_mode="reflect")); it needs T > pad and has
+ * frames 0 .. T / hop.  Without it pad = 0 and the frames are 0 ..
+ * (T - n_fft) / hop.  The caller asks for n_frames <= that count (Whisper:
+ * T / hop, which drops the last).
+ *
+ * Tables, computed in float64 and rounded once to float32:
+ *   w[n] = 0.5 - 0.5 cos(2 pi n / n_fft)           (periodic Hann)
+ *   Cw[k][n] = w[n] cos(2 pi ((k n) mod n_fft) / n_fft),  Sw[k][n] = -w[n] sin(..)
+ *   Wm[m][k]: librosa.filters.mel's defaults -- Slaney's scale, triangles
+ *   between n_mels + 2 points equally spaced in mel, each scaled by 2 / (its
+ *   width in Hz); filter m's non-zero entries are k in [lo_m, hi_m].
+ *
+ * Features, all float32:
+ *   re = im = +0;  for n = 0 .. n_fft-1: re = fmaf(Cw[k][n], xr[..], re), im alike
+ *   p[k] = fmaf(re, re, im * im)                   (the product rounded first)
+ *   mel = +0;  for k = lo_m .. hi_m: mel = fmaf(Wm[m][k], p[k], mel)
+ *   y[m][f] = mp3g_log10f(max(mel, 1e-10f))
+ * -- each sum ONE FMA chain in ascending order; the order is part of the
+ * contract.  mp3g_log10f (go-mp3_amd/csrc/logmel_log10.h) is built from integer
+ * operations and explicit FMAs only and compiled by host and device alike; it
+ * is within half an ulp of its result + 2^-45 of log10.  MP3G_LOGMEL_CLAMP then
+ * takes mx = the maximum of y over the n_mels x n_frames features of the row
+ * and plane and replaces y by (max(y, mx - 8.0f) + 4.0f) * 0.25f.
+ *
+ * Domain: finite samples with |x| <= 2^20; float32 subnormals are kept.
+ * Output: float [row][plane][n_mels][frame_stride], n_frames features written
+ * per mel row, nothing else. */
+#define MP3G_LOGMEL_CENTER 1u
+#define MP3G_LOGMEL_CLAMP 2u
+#define MP3G_LOGMEL_MIN_FFT 16
+#define MP3G_LOGMEL_MAX_FFT 1024
+#define MP3G_LOGMEL_MAX_MELS 128
+typedef struct mp3g_logmel mp3g_logmel;
+/* Builds the tables; device >= 0 also uploads them to that device (once),
+ * device = -1 makes a host-only object. */
+int mp3g_logmel_create(int device, int rate, int n_fft, int hop, int n_mels, double fmin, double fmax,
+                       uint32_t flags, mp3g_logmel** out);
+void mp3g_logmel_free(mp3g_logmel* lm);
+/* K, the host tables Cw and Sw float [K][n_fft] and Wm float [n_mels][K], the
+ * supports uint32 [n_mels][2] = lo_m, hi_m (lo > hi: an empty filter) -- all
+ * owned by the object -- and the frames a workgroup of the device call
+ * produces (any may be NULL). */
+int mp3g_logmel_info(const mp3g_logmel* lm, uint32_t* K, const float** cw, const float** sw, const float** wm,
+                     const uint32_t** support, uint32_t* tile_frames);
+/* The frames a row of T samples has (0: none, or T >= 2^62). */
+uint64_t mp3g_logmel_frames(const mp3g_logmel* lm, uint64_t T);
+/* The definition above in plain C++ (the reference the device call equals):
+ * out[m * frame_stride + f] for m < n_mels, f < n_frames <= mp3g_logmel_frames. */
+int mp3g_logmel_host(const mp3g_logmel* lm, const float* x, uint64_t T, uint64_t n_frames, float* out,
+                     uint64_t frame_stride);
+/* d_src: float [n_rows][n_planes][T]; d_out: float [n_rows][n_planes][n_mels]
+ * [frame_stride].  Both are device pointers and the launch shape depends on
+ * none of their contents: asynchronous on hip_stream and graph-capturable.
+ * T < 2^31; n_frames <= mp3g_logmel_frames(lm, T), frame_stride >= n_frames.
+ * Executions of one MP3G_LOGMEL_CLAMP object must be ordered on the device (one
+ * stream, or streams synchronised between them): they share the object's
+ * buffer of row maxima.  One object per stream for concurrent launches. */
+int mp3g_logmel_execute(const mp3g_logmel* lm, const float* d_src, uint32_t n_rows, uint32_t n_planes, uint32_t T,
+                        float* d_out, uint32_t n_frames, uint32_t frame_stride, void* hip_stream);
+/* Test hook: y[i] = mp3g_log10f(x[i]) (normal positive finite x). */
+void mp3g_logmel_log10f(const float* x, uint64_t n, float* y);
 
 /* ---- decoder: mp3.NewDecoder / io.Reader / io.Seeker (decode.go:27-388) ----
  * Scans on the host with read-ahead (headers, side info, reservoir) and
