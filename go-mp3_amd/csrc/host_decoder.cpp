@@ -14,14 +14,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <new>
-#include <thread>
 #include <vector>
 
 #include "../../include/mp3g.h"
@@ -31,27 +29,15 @@
 
 using namespace mp3g;
 using host::St;
+using host::to_status;
 
 namespace {
-
-int to_status(St s) {
-  switch (s) {
-    case St::kOk: return MP3G_OK;
-    case St::kEof: return MP3G_EOF;
-    case St::kErr: return MP3G_ERR_PARSE;
-    case St::kPanic: return MP3G_ERR_UNSUPPORTED;
-    case St::kRead: return MP3G_ERR_READ;
-  }
-  return MP3G_ERR_PARSE;
-}
 
 // Parses a whole stream (NewDecoder + reading to the end): tags skipped,
 // reservoir carried, stops at EOF or at the first failing frame.
 St parse_all(const uint8_t* data, size_t len, std::vector<mp3g_granule>* g, std::vector<int16_t>* c) {
   host::Source src;
-  src.data = data;
-  src.len = (int64_t)len;
-  St st = src.skip_tags();
+  St st = src.open_memory(data, len);
   if (st != St::kOk) return st;
   host::FrameParser parser;
   host::ParsedFrame f;
@@ -744,17 +730,9 @@ int mp3g_parse_streams(uint32_t n_streams, const uint8_t* const* datas, const si
   if (!granules || !coeffs || !n_granules) return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "null output");
   std::vector<std::vector<mp3g_granule>> g(n_streams);
   std::vector<std::vector<int16_t>> c(n_streams);
-  std::atomic<uint32_t> next{0};
-  auto work = [&]() {
-    for (uint32_t s; (s = next.fetch_add(1)) < n_streams;)
-      end_status[s] = to_status(parse_all(datas[s], lens[s], &g[s], &c[s]));
-  };
-  const int nt = std::max(1, std::min<int>(n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency(),
-                                           (int)std::max<uint32_t>(1, n_streams)));
-  std::vector<std::thread> pool;
-  for (int t = 1; t < nt; t++) pool.emplace_back(work);
-  work();
-  for (auto& t : pool) t.join();
+  parallel_for(0, n_streams, thread_count(n_threads, n_streams), [&](uint32_t s) {
+    end_status[s] = to_status(parse_all(datas[s], lens[s], &g[s], &c[s]));
+  });
   uint64_t total = 0;
   for (uint32_t s = 0; s < n_streams; s++) {
     streams[s].first_granule = total;

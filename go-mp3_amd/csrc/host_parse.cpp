@@ -584,8 +584,15 @@ St Source::skip_tags() {  // source.go:42-83
   }
 }
 
+St Source::open_memory(const uint8_t* bytes, size_t n) {
+  data = bytes;
+  len = (int64_t)n;
+  return skip_tags();
+}
+
 // ---- frameheader.go -------------------------------------------------------------
 int header_granules(uint32_t h) { return 2 >> h_lsf(h); }
+int header_channels(uint32_t h) { return h_nch(h); }
 int header_bytes_per_frame(uint32_t h) { return 576 * header_granules(h) * 4; }
 int header_sample_rate(uint32_t h) {  // frameheader.go:304-318
   const int lsf = h_lsf(h);
@@ -623,33 +630,109 @@ St read_header(Source& s, int64_t* pos_io, uint32_t* out) {  // frameheader.go:2
   return St::kOk;
 }
 
+// ---- frame-level rules: the header walk and the frame front -------------------
+// A frame-level rule (a version, a layer, a size limit) is stated in two
+// places: frame_layout, for the readers of headers alone (prescan, walk_frames),
+// and read_frame_front, which takes its sizes from it (FrameParser, FrameScanner).
+namespace {
+
+// What a header word alone says of its frame.
+struct FrameLayout {
+  int fsize;      // header_frame_size: the frame with its header
+  int crc;        // CRC bytes behind the header
+  int side_info;  // side-info bytes
+  int size;       // main-data bytes
+  bool walkable;  // passes the checks of read_frame_front that need no side info
+  int body() const { return crc + side_info + size; }  // the bytes behind the header
+};
+
+inline FrameLayout frame_layout(uint32_t h) {
+  FrameLayout l;
+  l.fsize = header_frame_size(h);
+  l.crc = h_protection(h) == 0 ? 2 : 0;
+  l.side_info = h_side_info_size(h);
+  l.size = l.fsize - l.side_info - 4 - l.crc;
+  l.walkable = h_id(h) != 0 && h_layer(h) == 1 && l.fsize >= 0 && l.fsize <= 2000 && l.size <= 1500 && l.size >= 0;
+  return l;
+}
+
+// The header walk from the source's position: sync search, the header's
+// layout, the frame's other bytes skipped; frame(h, layout) after every frame
+// that is walkable and all there, until it returns false.  Returns whether
+// the stream ended the walk (no header, not walkable, cut short), not `frame`.
+template <class Frame>
+inline bool walk_headers(Source& src, Frame&& frame) {
+  uint8_t skip[2048];
+  for (;;) {
+    uint32_t h;
+    int64_t pos = src.pos;
+    if (read_header(src, &pos, &h) != St::kOk) return true;
+    const FrameLayout l = frame_layout(h);
+    if (!l.walkable) return true;
+    bool sr;
+    if (src.read_full(skip, l.body(), &sr) < l.body()) return true;
+    if (!frame(h, l)) return false;
+  }
+}
+
+// ---- frame.Read up to the main data (frame.go:67-98) ----
+struct FrameFront {
+  uint32_t header;
+  int64_t start;  // frame position (frameheader.Read's)
+  SideInfo si;
+  int size;  // main-data bytes
+};
+
+// The front of a frame at the source's position, in the reference's order (a
+// short read of the CRC is an EOF before the version is a parse error): the
+// order gives every malformed input its status and source position.
+St read_frame_front(Source& s, FrameFront* f) {
+  f->start = s.pos;
+  St st = read_header(s, &f->start, &f->header);
+  if (st != St::kOk) return st;
+  const uint32_t h = f->header;
+  const FrameLayout l = frame_layout(h);
+  if (l.crc) {
+    uint8_t crc[2];
+    bool sr;
+    if (s.read_full(crc, l.crc, &sr) < l.crc) return sr ? St::kEof : St::kErr;
+  }
+  if (h_id(h) == 0) return St::kErr;     // MPEG 2.5
+  if (h_layer(h) != 1) return St::kErr;  // layer III only
+  st = read_side_info(s, h, &f->si);
+  if (st != St::kOk) return st;
+  if (l.fsize > 2000) return St::kErr;
+  if (l.size > 1500) return St::kErr;
+  if (l.size < 0) return St::kPanic;  // make([]byte, <0) panics
+  f->size = l.size;
+  return St::kOk;
+}
+
+// The side-info fields of a granule descriptor's channel.
+void side_info_fields(const SideInfo& si, int gr, int ch, mp3g_channel* c) {
+  c->global_gain = (uint8_t)si.global_gain[gr][ch];
+  c->scalefac_scale = (uint8_t)si.scalefac_scale[gr][ch];
+  c->preflag = (uint8_t)si.preflag[gr][ch];
+  c->win_switch_flag = (uint8_t)si.win_switch_flag[gr][ch];
+  c->block_type = (uint8_t)si.block_type[gr][ch];
+  c->mixed_block_flag = (uint8_t)si.mixed_block_flag[gr][ch];
+  for (int w = 0; w < 3; w++) c->subblock_gain[w] = (uint8_t)si.subblock_gain[gr][ch][w];
+}
+
+}  // namespace
+
 void prescan(const uint8_t* data, size_t len, uint64_t* n_granules, uint64_t* md_bytes) {
   // counted in locals, stored once: callers pass neighbouring elements of one
   // array per stream, and a store per frame from many threads into one cache
   // line serialised the pre-pass (8 threads no faster than 1)
   uint64_t ng = 0, nmd = 0;
-  *n_granules = *md_bytes = 0;
   Source src;
-  src.data = data;
-  src.len = (int64_t)len;
-  if (src.skip_tags() != St::kOk) return;
-  uint8_t skip[2048];
-  for (;;) {  // the checks of FrameScanner::next that need no side info
-    uint32_t h;
-    int64_t pos = src.pos;
-    if (read_header(src, &pos, &h) != St::kOk) break;
-    const int crc = h_protection(h) == 0 ? 2 : 0;
-    if (h_id(h) == 0 || h_layer(h) != 1) break;
-    const int fsize = header_frame_size(h);
-    if (fsize < 0 || fsize > 2000) break;
-    const int sis = h_side_info_size(h);
-    const int size = fsize - sis - 4 - crc;
-    if (size > 1500 || size < 0) break;
-    bool sr;
-    if (src.read_full(skip, crc + sis + size, &sr) < crc + sis + size) break;
-    ng += (uint64_t)header_granules(h);
-    nmd += (uint64_t)size;
-  }
+  if (src.open_memory(data, len) == St::kOk)
+    walk_headers(src, [&](uint32_t h, const FrameLayout& l) {
+      ng += (uint64_t)header_granules(h);
+      nmd += (uint64_t)l.size;
+      return true;
+    });
   *n_granules = ng;
   *md_bytes = nmd;
 }
@@ -657,35 +740,20 @@ void prescan(const uint8_t* data, size_t len, uint64_t* n_granules, uint64_t* md
 bool walk_frames(Source& src, uint64_t stop_granules, std::vector<WalkFrame>* frames, uint64_t* n_granules,
                  Source::Mark* end_at) {
   uint64_t ng = 0;
-  uint8_t skip[2048];
-  bool ended = false;
-  *end_at = src.mark();
-  while (ng < stop_granules) {  // prescan's checks, frame by frame
+  *end_at = src.mark();  // in front of the next frame, throughout
+  const bool ended = stop_granules > 0 && walk_headers(src, [&](uint32_t h, const FrameLayout& l) {
     WalkFrame f;
-    f.at = src.mark();
-    *end_at = f.at;
-    uint32_t h;
-    int64_t pos = src.pos;
-    ended = true;
-    if (read_header(src, &pos, &h) != St::kOk) break;
-    f.offset = src.rpos - 4;  // (the unread bytes went first: the header's last byte came from the source)
-    const int crc = h_protection(h) == 0 ? 2 : 0;
-    if (h_id(h) == 0 || h_layer(h) != 1) break;
-    const int fsize = header_frame_size(h);
-    if (fsize < 0 || fsize > 2000) break;
-    const int sis = h_side_info_size(h);
-    const int size = fsize - sis - 4 - crc;
-    if (size > 1500 || size < 0) break;
-    bool sr;
-    if (src.read_full(skip, crc + sis + size, &sr) < crc + sis + size) break;
-    ended = false;
+    f.at = *end_at;
+    // (the unread bytes went first: the frame's last byte came from the source)
+    f.offset = src.rpos - l.body() - 4;
     f.header = h;
-    f.md_bytes = (uint32_t)size;
+    f.md_bytes = (uint32_t)l.size;
     f.first_granule = ng;
     frames->push_back(f);
     ng += (uint64_t)header_granules(h);
     *end_at = src.mark();
-  }
+    return ng < stop_granules;
+  });
   *n_granules = ng;
   return ended;
 }
@@ -693,26 +761,12 @@ bool walk_frames(Source& src, uint64_t stop_granules, std::vector<WalkFrame>* fr
 // ---- frame.Read (frame.go:67-115) + maindata.Read (maindata.go:85-117, :290-323) ----
 St FrameParser::next(Source& s, ParsedFrame* out) {
   std::call_once(g_lut_once, build_lut);
-  uint32_t h;
-  int64_t pos = s.pos;
-  St st = read_header(s, &pos, &h);
+  FrameFront front;
+  St st = read_frame_front(s, &front);
   if (st != St::kOk) return st;
-  if (h_protection(h) == 0) {
-    uint8_t crc[2];
-    bool sr;
-    if (s.read_full(crc, 2, &sr) < 2) return sr ? St::kEof : St::kErr;
-  }
-  if (h_id(h) == 0) return St::kErr;     // MPEG 2.5
-  if (h_layer(h) != 1) return St::kErr;  // layer III only
-  SideInfo si;
-  st = read_side_info(s, h, &si);
-  if (st != St::kOk) return st;
-  const int fsize = header_frame_size(h);
-  if (fsize > 2000) return St::kErr;
-  int size = fsize - h_side_info_size(h) - 4;
-  if (h_protection(h) == 0) size -= 2;
-  if (size > 1500) return St::kErr;
-  if (size < 0) return St::kPanic;  // make([]byte, <0) panics
+  const uint32_t h = front.header;
+  SideInfo& si = front.si;
+  const int size = front.size;
   // reservoir: keep main_data_begin bytes of the previous main data (or, on
   // underflow, all of it -- the reference appends without an error)
   const int offset = si.main_data_begin;
@@ -736,7 +790,7 @@ St FrameParser::next(Source& s, ParsedFrame* out) {
 
   const int ng = header_granules(h), nch = h_nch(h);
   out->header = h;
-  out->start = pos;
+  out->start = front.start;
   out->n_granules = ng;
   for (int gr = 0; gr < ng; gr++) {
     mp3g_granule& G = out->gran[gr];
@@ -746,14 +800,8 @@ St FrameParser::next(Source& s, ParsedFrame* out) {
     G.gr = (uint32_t)gr;
     for (int ch = 0; ch < nch; ch++) {
       mp3g_channel& c = G.ch[ch];
+      side_info_fields(si, gr, ch, &c);
       c.count1 = (uint16_t)si.count1[gr][ch];
-      c.global_gain = (uint8_t)si.global_gain[gr][ch];
-      c.scalefac_scale = (uint8_t)si.scalefac_scale[gr][ch];
-      c.preflag = (uint8_t)si.preflag[gr][ch];
-      c.win_switch_flag = (uint8_t)si.win_switch_flag[gr][ch];
-      c.block_type = (uint8_t)si.block_type[gr][ch];
-      c.mixed_block_flag = (uint8_t)si.mixed_block_flag[gr][ch];
-      for (int w = 0; w < 3; w++) c.subblock_gain[w] = (uint8_t)si.subblock_gain[gr][ch][w];
       for (int k = 0; k < 22; k++) c.scalefac_l[k] = (uint8_t)md.scalefac_l[gr][ch][k];
       for (int k = 0; k < 13; k++)
         for (int w = 0; w < 3; w++) c.scalefac_s[k][w] = (uint8_t)md.scalefac_s[gr][ch][k][w];
@@ -795,9 +843,6 @@ int64_t sf_end(int64_t pos, int64_t end, const mp3g_hjob& j) {
   return pos;
 }
 
-}  // namespace
-
-namespace {
 // appends to the main-data sinks (n bytes in use afterwards)
 bool md_resize(std::vector<uint8_t>* v, size_t n) {
   v->resize(n);
@@ -820,27 +865,12 @@ St FrameScanner::next(Source& s, ScannedFrame* out, RawMd* md) { return next_imp
 
 template <class Md>
 St FrameScanner::next_impl(Source& s, ScannedFrame* out, Md* md) {
-  // header, CRC, side info and sizes exactly as FrameParser::next
-  uint32_t h;
-  int64_t pos = s.pos;
-  St st = read_header(s, &pos, &h);
+  FrameFront front;
+  const St st = read_frame_front(s, &front);
   if (st != St::kOk) return st;
-  if (h_protection(h) == 0) {
-    uint8_t crc[2];
-    bool sr;
-    if (s.read_full(crc, 2, &sr) < 2) return sr ? St::kEof : St::kErr;
-  }
-  if (h_id(h) == 0) return St::kErr;
-  if (h_layer(h) != 1) return St::kErr;
-  SideInfo si;
-  st = read_side_info(s, h, &si);
-  if (st != St::kOk) return st;
-  const int fsize = header_frame_size(h);
-  if (fsize > 2000) return St::kErr;
-  int size = fsize - h_side_info_size(h) - 4;
-  if (h_protection(h) == 0) size -= 2;
-  if (size > 1500) return St::kErr;
-  if (size < 0) return St::kPanic;
+  const uint32_t h = front.header;
+  const SideInfo& si = front.si;
+  const int size = front.size;
 
   // reservoir (maindata.go:290-323): the frame's bit buffer is the suffix of
   // the main-data concatenation starting at `vstart` -- the tail of the
@@ -871,7 +901,7 @@ St FrameScanner::next_impl(Source& s, ScannedFrame* out, Md* md) {
 
   const int lsf = h_lsf(h), nch = h_nch(h), ng = header_granules(h);
   out->header = h;
-  out->start = pos;
+  out->start = front.start;
   out->n_granules = ng;
   std::memset(out->gran, 0, sizeof out->gran);
   std::memset(out->job, 0, sizeof out->job);
@@ -882,13 +912,7 @@ St FrameScanner::next_impl(Source& s, ScannedFrame* out, Md* md) {
     G.gr = (uint32_t)gr;
     for (int ch = 0; ch < nch; ch++) {
       mp3g_channel& c = G.ch[ch];
-      c.global_gain = (uint8_t)si.global_gain[gr][ch];
-      c.scalefac_scale = (uint8_t)si.scalefac_scale[gr][ch];
-      c.preflag = (uint8_t)si.preflag[gr][ch];
-      c.win_switch_flag = (uint8_t)si.win_switch_flag[gr][ch];
-      c.block_type = (uint8_t)si.block_type[gr][ch];
-      c.mixed_block_flag = (uint8_t)si.mixed_block_flag[gr][ch];
-      for (int w = 0; w < 3; w++) c.subblock_gain[w] = (uint8_t)si.subblock_gain[gr][ch][w];
+      side_info_fields(si, gr, ch, &c);  // (scale factors and count1 stay zero: the device's)
 
       mp3g_hjob& J = out->job[gr][ch];
       J.part2_start = (uint64_t)bit;

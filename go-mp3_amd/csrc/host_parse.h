@@ -25,6 +25,18 @@ namespace host {
 // caller's io.Reader failed (decode.go:48-63 passes its error through).
 enum class St { kOk = 0, kEof = 1, kErr = 2, kPanic = 3, kRead = 4 };
 
+// The C-ABI status (include/mp3g.h) of an St.
+inline int to_status(St s) {
+  switch (s) {
+    case St::kOk: return MP3G_OK;
+    case St::kEof: return MP3G_EOF;
+    case St::kErr: return MP3G_ERR_PARSE;
+    case St::kPanic: return MP3G_ERR_UNSUPPORTED;
+    case St::kRead: return MP3G_ERR_READ;
+  }
+  return MP3G_ERR_PARSE;
+}
+
 // source.go (source.go:22-122) over one of two byte sources:
 //  * in memory (data, len): a bytes.Reader; seekable = implements io.Seeker;
 //  * reader mode (rd != nullptr): the caller's io.Reader / io.Seeker as
@@ -59,6 +71,9 @@ struct Source {
   void unread_bytes(const uint8_t* b, int n);
   bool seek(int64_t off, int whence, int64_t* res);
   St skip_tags();
+  // A fresh Source over caller memory (a seekable bytes.Reader), tags skipped:
+  // NewDecoder up to the first frame.  Returns skip_tags' status.
+  St open_memory(const uint8_t* bytes, size_t n);
 
   // Position state for a rollback (reader mode: the window keeps the bytes
   // from keep_from on, so a restore never needs the reader again).
@@ -167,8 +182,8 @@ St read_header(Source& s, int64_t* pos_io, uint32_t* out);
 // that scans to EOF).
 void prescan(const uint8_t* data, size_t len, uint64_t* n_granules, uint64_t* md_bytes);
 
-// The same walk (prescan's checks, after skip_tags), keeping one record per
-// frame: where the scanner can be restarted at it, its header, main-data
+// The same walk from the source's position (after the tags), keeping one
+// record per frame: where the scanner can be restarted at it, its header, main-data
 // bytes and first granule.  Stops once `stop_granules` granules are covered
 // (~0 = the stream's end); *end_at is the source state at the first frame not
 // walked (where FrameScanner::next yields the stream's end status when the
@@ -188,6 +203,7 @@ int header_bytes_per_frame(uint32_t h);
 int header_frame_size(uint32_t h);
 int header_sample_rate(uint32_t h);
 int header_granules(uint32_t h);
+int header_channels(uint32_t h);
 
 }  // namespace host
 }  // namespace mp3g

@@ -14,7 +14,6 @@
 #include <memory>
 #include <mutex>
 #include <new>
-#include <thread>
 #include <vector>
 
 #include "../../include/mp3g.h"
@@ -24,6 +23,7 @@
 
 using namespace mp3g;
 using host::St;
+using host::to_status;
 
 namespace {
 
@@ -77,17 +77,6 @@ struct mp3g_scan {
 
 namespace {
 
-int to_status(St s) {
-  switch (s) {
-    case St::kOk: return MP3G_OK;
-    case St::kEof: return MP3G_EOF;
-    case St::kErr: return MP3G_ERR_PARSE;
-    case St::kPanic: return MP3G_ERR_UNSUPPORTED;
-    case St::kRead: return MP3G_ERR_READ;
-  }
-  return MP3G_ERR_PARSE;
-}
-
 struct StreamScan {
   std::vector<mp3g_granule> gran;
   std::vector<mp3g_hjob> jobs;  // positions relative to md
@@ -98,9 +87,7 @@ struct StreamScan {
 // NewDecoder + reading to the end (as host_decoder.cpp parse_all).
 void scan_all(const uint8_t* data, size_t len, StreamScan* out) {
   host::Source src;
-  src.data = data;
-  src.len = (int64_t)len;
-  St st = src.skip_tags();
+  St st = src.open_memory(data, len);
   if (st != St::kOk) {
     out->end = st;
     return;
@@ -130,10 +117,8 @@ void scan_all(const uint8_t* data, size_t len, StreamScan* out) {
 uint64_t scan_into(const uint8_t* data, size_t len, mp3g_granule* gran, mp3g_hjob* jobs, uint64_t cap,
                    host::RawMd* md, St* end, bool* overflow) {
   host::Source src;
-  src.data = data;
-  src.len = (int64_t)len;
   *overflow = false;
-  St st = src.skip_tags();
+  St st = src.open_memory(data, len);
   if (st != St::kOk) {
     *end = st;
     return 0;
@@ -161,7 +146,7 @@ uint64_t scan_into(const uint8_t* data, size_t len, mp3g_granule* gran, mp3g_hjo
 
 // The stream's end status at `at`, the first frame a header walk did not
 // accept: what FrameScanner::next returns there (its checks do not depend on
-// the reservoir).
+// the reservoir; a frame it accepts has no room in the sink).
 St end_status_at(host::Source& src, const host::Source::Mark& at) {
   src.restore(at);
   host::FrameScanner sc;
@@ -195,9 +180,7 @@ St end_status_at(host::Source& src, const host::Source::Mark& at) {
 void scan_window(const uint8_t* data, size_t len, const mp3g_window& w, StreamScan* out, mp3g_window_row* row) {
   *row = mp3g_window_row{};
   host::Source src;
-  src.data = data;
-  src.len = (int64_t)len;
-  St st = src.skip_tags();
+  St st = src.open_memory(data, len);
   if (st != St::kOk) {
     out->end = st;
     return;
@@ -245,7 +228,6 @@ void scan_window(const uint8_t* data, size_t len, const mp3g_window& w, StreamSc
     }
     return a;
   };
-  auto stereo = [](uint32_t h) { return ((h >> 6) & 3u) != 3u; };
   // the replay start (the plans' rule, granule_fast.hip prologue): two
   // granules back, and back to the second-latest stereo granule before lo (the
   // only one when there is one) for channel 1's state across mono granules;
@@ -255,7 +237,7 @@ void scan_window(const uint8_t* data, size_t len, const mp3g_window& w, StreamSc
     int found = 0;
     uint64_t s_last = 0;
     for (size_t fi = frame_of(lo - 1) + 1; fi-- > 0 && found < 2;) {
-      if (!stereo(fr[fi].header)) continue;
+      if (host::header_channels(fr[fi].header) != 2) continue;
       const uint64_t g0 = fr[fi].first_granule, g1 = std::min<uint64_t>(g0 + host::header_granules(fr[fi].header), lo);
       for (uint64_t g = g1; g-- > g0 && found < 2;) {
         found++;
@@ -303,36 +285,37 @@ void scan_window(const uint8_t* data, size_t len, const mp3g_window& w, StreamSc
   row->n_valid = (uint32_t)std::min<uint64_t>(T, avail_end - start);
 }
 
-// fn(k) for k in [k0, k1) on up to nt threads (the calling thread included)
-template <class Fn>
-void parallel_for(uint32_t k0, uint32_t k1, int nt, Fn&& fn) {
-  std::atomic<uint32_t> next{k0};
-  auto work = [&]() {
-    for (uint32_t k; (k = next.fetch_add(1)) < k1;) fn(k);
-  };
-  nt = std::max(1, std::min<int>(nt, (int)(k1 - k0)));
-  std::vector<std::thread> pool;
-  for (int t = 1; t < nt; t++) pool.emplace_back(work);
-  work();
-  for (auto& t : pool) t.join();
+// Where the streams of a batch land in the concatenation, from each stream's
+// granules and main-data bytes: prefix sums ([n_streams + 1]), every stream's
+// main data 16-B aligned, and kMdTail zero bytes behind the last stream's (the
+// device reads whole 8-B words): a main-data buffer is m_at.back() + kMdTail.
+constexpr size_t kMdTail = 16;
+void batch_layout(const std::vector<uint64_t>& granules, const std::vector<uint64_t>& md_bytes,
+                  std::vector<uint64_t>* g_at, std::vector<uint64_t>* m_at) {
+  g_at->assign(granules.size() + 1, 0);
+  m_at->assign(granules.size() + 1, 0);
+  for (size_t k = 0; k < granules.size(); k++) {
+    (*g_at)[k + 1] = (*g_at)[k] + granules[k];
+    (*m_at)[k + 1] = (*m_at)[k] + ((md_bytes[k] + 15) & ~(uint64_t)15);
+  }
 }
 
 // The per-stream scans concatenated into *s (the two-step path of
 // mp3g_scan_streams, and mp3g_scan_windows): job positions become absolute.
 bool merge_scans(std::vector<StreamScan>& per, int nt, mp3g_scan* s) {
   const uint32_t n_streams = (uint32_t)per.size();
-  // where each stream lands; each stream's main data 16-B aligned, 16 zero
-  // bytes of padding after the last (the device reads whole 8-B words)
-  std::vector<uint64_t> g_at(n_streams + 1), m_at(n_streams + 1);
+  std::vector<uint64_t> pg(n_streams), pm(n_streams);
   for (uint32_t k = 0; k < n_streams; k++) {
-    g_at[k + 1] = g_at[k] + per[k].gran.size();
-    m_at[k + 1] = m_at[k] + ((per[k].md.size() + 15) & ~(size_t)15);
+    pg[k] = per[k].gran.size();
+    pm[k] = per[k].md.size();
   }
+  std::vector<uint64_t> g_at, m_at;
+  batch_layout(pg, pm, &g_at, &m_at);
   const uint64_t ng = g_at[n_streams], nmd = m_at[n_streams];
-  if (!s->gran.alloc(ng) || !s->jobs.alloc(2 * ng) || !s->md.alloc(nmd + 16)) return false;
+  if (!s->gran.alloc(ng) || !s->jobs.alloc(2 * ng) || !s->md.alloc(nmd + kMdTail)) return false;
   s->streams.resize(n_streams);
   s->status.resize(n_streams);
-  std::memset(s->md.data() + nmd, 0, 16);
+  std::memset(s->md.data() + nmd, 0, kMdTail);
   parallel_for(0, n_streams, nt, [&](uint32_t k) {
     StreamScan& p = per[k];
     const uint64_t g = g_at[k], m = m_at[k];
@@ -494,18 +477,7 @@ int mp3g_scan_streams(uint32_t n_streams, const uint8_t* const* datas, const siz
   mp3g_scan* s = new (std::nothrow) mp3g_scan;
   if (!s) return abi_fail(MP3G_ERR_OUT_OF_MEMORY, "scan");
   std::vector<StreamScan> per(n_streams);
-  const int nt = std::max(1, std::min<int>(n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency(),
-                                           (int)std::max<uint32_t>(1, n_streams)));
-  auto parallel = [&](auto&& fn) {  // fn(k) for every stream, on nt threads
-    std::atomic<uint32_t> next{0};
-    auto work = [&]() {
-      for (uint32_t k; (k = next.fetch_add(1)) < n_streams;) fn(k);
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nt; t++) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-  };
+  const int nt = thread_count(n_threads, n_streams);
   // Direct path: a header-only pre-pass sizes every stream, then each stream
   // is scanned straight into its place in the concatenation (no per-stream
   // buffers, no merge copy).  A stream whose side info ends it before the
@@ -513,21 +485,18 @@ int mp3g_scan_streams(uint32_t n_streams, const uint8_t* const* datas, const siz
   // batch to the two-step path below.
   {
     std::vector<uint64_t> pg(n_streams), pm(n_streams);
-    parallel([&](uint32_t k) { host::prescan(datas[k], lens[k], &pg[k], &pm[k]); });
-    std::vector<uint64_t> g_at(n_streams + 1), m_at(n_streams + 1);
-    for (uint32_t k = 0; k < n_streams; k++) {
-      g_at[k + 1] = g_at[k] + pg[k];
-      m_at[k + 1] = m_at[k] + ((pm[k] + 15) & ~(uint64_t)15);
-    }
+    parallel_for(0, n_streams, nt, [&](uint32_t k) { host::prescan(datas[k], lens[k], &pg[k], &pm[k]); });
+    std::vector<uint64_t> g_at, m_at;
+    batch_layout(pg, pm, &g_at, &m_at);
     const uint64_t ng = g_at[n_streams], nmd = m_at[n_streams];
-    if (!s->gran.alloc(ng) || !s->jobs.alloc(2 * ng) || !s->md.alloc(nmd + 16)) {
+    if (!s->gran.alloc(ng) || !s->jobs.alloc(2 * ng) || !s->md.alloc(nmd + kMdTail)) {
       delete s;
       return abi_fail(MP3G_ERR_OUT_OF_MEMORY, "scan buffers");
     }
     s->streams.resize(n_streams);
     s->status.resize(n_streams);
     std::atomic<bool> ok{true};
-    parallel([&](uint32_t k) {
+    parallel_for(0, n_streams, nt, [&](uint32_t k) {
       host::RawMd md;
       md.base = s->md.data();
       md.n = m_at[k];
@@ -544,7 +513,7 @@ int mp3g_scan_streams(uint32_t n_streams, const uint8_t* const* datas, const siz
       s->streams[k].n_granules = (uint32_t)n;
       s->streams[k].flags = 0;
       s->status[k] = to_status(end);
-      std::memset(&s->md[md.n], 0, m_at[k + 1] + (k + 1 == n_streams ? 16 : 0) - md.n);
+      std::memset(&s->md[md.n], 0, m_at[k + 1] + (k + 1 == n_streams ? kMdTail : 0) - md.n);
     });
     if (ok) {
       *out = s;
@@ -553,7 +522,7 @@ int mp3g_scan_streams(uint32_t n_streams, const uint8_t* const* datas, const siz
     s->streams.clear();
     s->status.clear();
   }
-  parallel([&](uint32_t k) { scan_all(datas[k], lens[k], &per[k]); });
+  parallel_for(0, n_streams, nt, [&](uint32_t k) { scan_all(datas[k], lens[k], &per[k]); });
 
   if (!merge_scans(per, nt, s)) {
     delete s;
@@ -572,8 +541,7 @@ int mp3g_scan_windows(uint32_t n_streams, const uint8_t* const* datas, const siz
       return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "scan_windows: window");
   mp3g_scan* s = new (std::nothrow) mp3g_scan;
   if (!s) return abi_fail(MP3G_ERR_OUT_OF_MEMORY, "scan");
-  const int nt = std::max(1, std::min<int>(n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency(),
-                                           (int)std::max<uint32_t>(1, n_streams)));
+  const int nt = thread_count(n_threads, n_streams);
   std::vector<StreamScan> per(n_streams);
   s->rows.resize(n_streams);
   s->windowed = true;
@@ -592,21 +560,18 @@ int mp3g_scan_windows(uint32_t n_streams, const uint8_t* const* datas, const siz
 int mp3g_stream_rates(uint32_t n_streams, const uint8_t* const* datas, const size_t* lens, int n_threads, int* rates,
                       int* channels) {
   if (n_streams && (!datas || !lens)) return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "null argument");
-  const int nt = std::max(1, std::min<int>(n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency(),
-                                           (int)std::max<uint32_t>(1, n_streams)));
+  const int nt = thread_count(n_threads, n_streams);
   parallel_for(0, n_streams, nt, [&](uint32_t k) {
     int rate = 0, nch = 0;
     host::Source src;
-    src.data = datas[k];
-    src.len = (int64_t)lens[k];
-    if (src.skip_tags() == St::kOk) {
+    if (src.open_memory(datas[k], lens[k]) == St::kOk) {
       std::vector<host::WalkFrame> fr;
       uint64_t ng = 0;
       host::Source::Mark end_at;
       (void)host::walk_frames(src, 1, &fr, &ng, &end_at);
       if (!fr.empty()) {
         rate = host::header_sample_rate(fr[0].header);
-        nch = ((fr[0].header >> 6) & 3u) == 3u ? 1 : 2;
+        nch = host::header_channels(fr[0].header);
       }
     }
     if (rates) rates[k] = rate;
@@ -734,16 +699,14 @@ int mp3g_decode_streams_into_out(int device, uint32_t n_streams, const uint8_t* 
   if (!n_granules || (n_streams && (!datas || !lens || !streams || !end_status)))
     return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "null argument");
   *n_granules = 0;
-  const int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
+  const int nt = thread_count(n_threads, n_streams);
   const PipeTrace trace;
   // ---- the layout: a header-only pre-pass over every stream ----
-  std::vector<uint64_t> pg(n_streams), pm(n_streams), g_at(n_streams + 1), m_at(n_streams + 1);
+  std::vector<uint64_t> pg(n_streams), pm(n_streams);
   parallel_for(0, n_streams, nt, [&](uint32_t k) { host::prescan(datas[k], lens[k], &pg[k], &pm[k]); });
   trace.mark("prescan");
-  for (uint32_t k = 0; k < n_streams; k++) {
-    g_at[k + 1] = g_at[k] + pg[k];
-    m_at[k + 1] = m_at[k] + ((pm[k] + 15) & ~(uint64_t)15);
-  }
+  std::vector<uint64_t> g_at, m_at;
+  batch_layout(pg, pm, &g_at, &m_at);
   const uint64_t total = g_at[n_streams];
   *n_granules = total;
   if (total > out_cap_granules) return abi_fail(MP3G_ERR_INVALID_ARGUMENT, "pcm holds fewer blocks than needed");
@@ -761,18 +724,8 @@ int mp3g_decode_streams_into_out(int device, uint32_t n_streams, const uint8_t* 
     // streams with no frame: their scan statuses
     for (uint32_t k = 0; k < n_streams; k++) {
       host::Source src;
-      src.data = datas[k];
-      src.len = (int64_t)lens[k];
-      St st = src.skip_tags();
-      if (st == St::kOk) {
-        host::FrameScanner sc;
-        host::ScannedFrame f;
-        uint8_t one[1];
-        host::RawMd md;
-        md.base = one;
-        st = sc.next(src, &f, &md);
-      }
-      end_status[k] = to_status(st == St::kOk ? St::kErr : st);
+      const St st = src.open_memory(datas[k], lens[k]);
+      end_status[k] = to_status(st == St::kOk ? end_status_at(src, src.mark()) : st);
     }
     return MP3G_OK;
   }
@@ -795,10 +748,10 @@ int mp3g_decode_streams_into_out(int device, uint32_t n_streams, const uint8_t* 
     max_ng = std::max(max_ng, g_at[cut[gi + 1]] - g_at[cut[gi]]);
     max_md = std::max(max_md, m_at[cut[gi + 1]] - m_at[cut[gi]]);
   }
-  // pinned arena per slot: [granules | jobs | main data + 16 | chunk table]
+  // pinned arena per slot: [granules | jobs | main data + kMdTail | chunk table]
   // (a plan without state flags has at most one chunk per granule)
   const size_t b_gran = max_ng * sizeof(mp3g_granule), b_jobs = 2 * max_ng * sizeof(mp3g_hjob);
-  const size_t b_md = (max_md + 16 + 15) & ~(size_t)15, b_chunks = max_ng * sizeof(ChunkDesc);
+  const size_t b_md = (max_md + kMdTail + 15) & ~(size_t)15, b_chunks = max_ng * sizeof(ChunkDesc);
   trace.mark("layout");
 
   int prev = -1;
@@ -907,7 +860,7 @@ int mp3g_decode_streams_into_out(int device, uint32_t n_streams, const uint8_t* 
         end_status[k] = to_status(end);
         std::memset(md + sink.n, 0, (size_t)(m_at[k + 1] - M0 - sink.n));
       });
-      std::memset(md + nmd, 0, 16);
+      std::memset(md + nmd, 0, kMdTail);
       trace.mark("scan", gi);
       if (overflow) {  // the pre-pass is an upper bound, so this cannot happen
         rc = abi_fail(MP3G_ERR_INVALID_ARGUMENT, "decode_streams_into: layout");
@@ -948,7 +901,7 @@ int mp3g_decode_streams_into_out(int device, uint32_t n_streams, const uint8_t* 
       if (e == hipSuccess) e = hipMemcpyAsync(B->d_gran[slot].p, gran, ng * sizeof(mp3g_granule), hipMemcpyHostToDevice, up);
       if (e == hipSuccess)
         e = hipMemcpyAsync(B->d_jobs[slot].p, jobs, 2 * ng * sizeof(mp3g_hjob), hipMemcpyHostToDevice, up);
-      if (e == hipSuccess) e = hipMemcpyAsync(B->d_md[slot].p, md, nmd + 16, hipMemcpyHostToDevice, up);
+      if (e == hipSuccess) e = hipMemcpyAsync(B->d_md[slot].p, md, nmd + kMdTail, hipMemcpyHostToDevice, up);
       if (e == hipSuccess && !chunks.empty())
         e = hipMemcpyAsync(B->d_chunks[slot].p, h_chunks, chunks.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice, up);
       if (e == hipSuccess) e = hipEventRecord(B->h2d[slot], up);

@@ -306,9 +306,7 @@ def parse_stream(data: bytes):
 
 def parse_streams(datas, n_threads=0):
     """Many streams in parallel: (granules, coeffs, streams[STREAM_DTYPE], end_status[])."""
-    bufs = [np.frombuffer(d, dtype=np.uint8) if len(d) else np.zeros(1, np.uint8) for d in datas]
-    ptrs = (C.c_void_p * max(1, len(bufs)))(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * max(1, len(bufs)))(*[len(d) for d in datas])
+    bufs, ptrs, lens = _stream_args(datas)
     streams = np.zeros(len(datas), STREAM_DTYPE)
     status = np.zeros(max(1, len(datas)), np.int32)
     g, c, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
@@ -591,6 +589,11 @@ def _scan_windows(datas, starts, lengths, gapless, n_threads=0):
     return _scan_result(h, B, time.perf_counter() - t0, rows=True)
 
 
+def _check_window_format(out_format):
+    if out_format not in (OUT_F32_PLANAR, OUT_F32_MONO):
+        raise Mp3gError(8 if out_bytes_per_granule(out_format) else 1, "windowed output is OUT_F32_PLANAR or OUT_F32_MONO")
+
+
 def decode_windows_tensor(datas, starts, n_samples, mode=MODE_EXACT, out_format=OUT_F32_PLANAR, gapless=False,
                           n_threads=0, device=0):
     """A crop of every stream, decoded straight into one dense batch tensor:
@@ -607,8 +610,7 @@ def decode_windows_tensor(datas, starts, n_samples, mode=MODE_EXACT, out_format=
     window was filled before the stream's end).  Runs on the current torch
     stream and returns when the kernels are done."""
     import torch
-    if out_format not in (OUT_F32_PLANAR, OUT_F32_MONO):
-        raise Mp3gError(8 if out_bytes_per_granule(out_format) else 1, "windowed output is OUT_F32_PLANAR or OUT_F32_MONO")
+    _check_window_format(out_format)
     s = scan_windows(datas, starts, n_samples, gapless=gapless, n_threads=n_threads)
     B, T = len(datas), int(n_samples)
     dev = torch.device("cuda", device)
@@ -750,8 +752,7 @@ def decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=MODE_EX
     int64[B], end_status of the windowed scan, rates int32[B] (0: no valid
     frame, an all-zero row)."""
     import torch
-    if out_format not in (OUT_F32_PLANAR, OUT_F32_MONO):
-        raise Mp3gError(8 if out_bytes_per_granule(out_format) else 1, "windowed output is OUT_F32_PLANAR or OUT_F32_MONO")
+    _check_window_format(out_format)
     if int(rate) <= 0:
         raise Mp3gError(1, "rate not positive")
     zeros, rolloff, beta = RESAMPLE_QUALITY[quality] if isinstance(quality, str) else quality

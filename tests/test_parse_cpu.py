@@ -122,3 +122,39 @@ def test_parse_streams_batch_matches_single(sample_files):
         lo, n = int(s[k]["first_granule"]), int(s[k]["n_granules"])
         assert n == len(g1) and st[k] == e1
         assert g[lo:lo + n].tobytes() == g1.tobytes() and np.array_equal(c[lo:lo + n], c1)
+
+
+def frame_header(version, layer, protection, bitrate, sfreq, padding=0, mode=0):
+    """The 4 header bytes: sync 0x7FF, then the fields as frameheader.go reads them."""
+    h = (0x7FF << 21) | (version << 19) | (layer << 17) | (protection << 16) | (bitrate << 12) | (sfreq << 10) | \
+        (padding << 9) | (mode << 6)
+    return h.to_bytes(4, "big")
+
+
+# (tail behind 4 good frames, granules, end status): the order of the checks at
+# the front of a frame (frame.go:67-98).  The first two rows tell the CRC read
+# from the version check: a reader that checked the version first would give
+# a parse error where the reference, short of CRC bytes, gives EOF.
+MPEG25 = frame_header(0, 1, 0, 9, 0)
+MPEG1 = frame_header(3, 1, 1, 9, 0)
+FRAME_FRONT_TAILS = [
+    ("MPEG-2.5, CRC cut", MPEG25 + bytes(1), 8, 7),
+    ("MPEG-2.5", MPEG25 + bytes(64), 8, 6),
+    ("cut in the side info", MPEG1 + bytes(10), 8, 7),
+    ("cut in the main data", MPEG1 + bytes(40), 8, 7),
+    ("free format", frame_header(3, 1, 1, 0, 0) + bytes(64), 8, 6),
+    ("cut in the header", MPEG1[:3], 8, 7),
+    ("24-byte MPEG-2 frame", frame_header(2, 1, 0, 1, 1) + bytes(200), 9, 7),
+]
+
+
+@pytest.mark.parametrize("what,tail,granules,end", FRAME_FRONT_TAILS, ids=[t[0] for t in FRAME_FRONT_TAILS])
+def test_frame_front_order(what, tail, granules, end):
+    from mp3g import synth
+    d = synth.encode_stream(1, 4) + tail
+    g, _, st = mp3g.parse_stream(d)
+    assert (len(g), st) == (granules, end), what
+    for s in (mp3g.scan_streams([d], n_threads=1), mp3g.scan_windows([d], [0], 1 << 20)):
+        assert (len(s["granules"]), int(s["streams"][0]["n_granules"]), int(s["end_status"][0])) == \
+            (granules, granules, end), what
+    assert oracle.decode_all_capture(d)[0] == {7: 0, 6: 2}[end], what  # ORC_OK, ORC_ERR
