@@ -157,6 +157,17 @@ def lib():
             L.mp3g_logmel_execute.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
             L.mp3g_logmel_log10f.argtypes = [vp, u64, vp]
             L.mp3g_logmel_log10f.restype = None
+        if hasattr(L, "mp3g_fbank_create"):  # (an older build through MP3G_LIB: A/B runs)
+            L.mp3g_fbank_create.argtypes = [C.c_int] * 5 + [C.c_double] * 4 + [C.c_int, u32, C.POINTER(vp)]
+            L.mp3g_fbank_free.argtypes = [vp]
+            L.mp3g_fbank_free.restype = None
+            L.mp3g_fbank_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)] + [C.POINTER(vp)] * 5 + [C.POINTER(u32)]
+            L.mp3g_fbank_frames.argtypes = [vp, u64]
+            L.mp3g_fbank_frames.restype = u64
+            L.mp3g_fbank_host.argtypes = [vp, vp, u64, u64, vp, u64]
+            L.mp3g_fbank_execute.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
+            L.mp3g_fbank_logf.argtypes = [vp, u64, vp]
+            L.mp3g_fbank_logf.restype = None
         L.mp3g_lame_parse.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo)]
         L.mp3g_lame_parse_reader.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo), C.POINTER(C.c_size_t)]
         L.mp3g_lame_total_delay.argtypes = [C.POINTER(_LameInfo)]
@@ -931,6 +942,156 @@ def decode_windows_logmel_tensor(datas, starts, n_samples, rate=16000, n_fft=400
     finally:
         lm.close()
     return feats, np.minimum(F, -(-lengths // lm.hop)), end_status, rates
+
+
+# ---- Kaldi filter-bank features of decoded rows (include/mp3g.h) -------------
+FBANK_REMOVE_DC = 1
+FBANK_SNIP_EDGES = 2
+FBANK_WINDOWS = {"povey": 0, "hamming": 1, "hanning": 2, "rectangular": 3}
+
+
+def logf(x):
+    """mp3g_logf of every element of x (float32; normal, positive, finite):
+    the filter-bank features' natural logarithm, for tests."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.empty_like(x)
+    lib().mp3g_fbank_logf(_ptr(x), x.size, _ptr(y))
+    return y
+
+
+class FBank:
+    """Kaldi's log mel filter-bank features of float32 rows (mp3g_fbank_*; what
+    compute-fbank-feats and torchaudio.compliance.kaldi.fbank compute, without
+    dither, energy, VTLN and subtract_mean): per frame DC removal and
+    pre-emphasis, the window, the power spectrum of the frame zero-padded to
+    P = the next power of two, Kaldi's mel triangles and the natural logarithm
+    floored at float32 epsilon, time-major.  Samples are multiplied by `scale`
+    first (Kaldi models read int16-range samples).  Every sum is ONE float32
+    FMA chain in ascending order, so the device call (execute) equals the host
+    reference (host) bit for bit.  device=None (or -1) makes a host-only
+    object; high_freq <= 0 means rate / 2 + high_freq."""
+
+    def __init__(self, rate=16000, frame_length_ms=25.0, frame_shift_ms=10.0, n_mels=80, low_freq=20.0, high_freq=0.0,
+                 preemphasis=0.97, remove_dc=True, window="povey", snip_edges=True, scale=32768.0, device=None):
+        self._h = C.c_void_p()
+        if window not in FBANK_WINDOWS:
+            raise Mp3gError(1, "FBank: window is one of " + ", ".join(FBANK_WINDOWS))
+        self.device = -1 if device is None else int(device)
+        self.rate, self.n_mels = int(rate), int(n_mels)
+        # Kaldi's conversion of the durations to samples
+        self.N, self.hop = int(self.rate * 0.001 * frame_length_ms), int(self.rate * 0.001 * frame_shift_ms)
+        self.preemphasis, self.scale, self.window = float(preemphasis), float(scale), window
+        self.remove_dc, self.snip_edges = bool(remove_dc), bool(snip_edges)
+        self.flags = (FBANK_REMOVE_DC if remove_dc else 0) | (FBANK_SNIP_EDGES if snip_edges else 0)
+        _check(lib().mp3g_fbank_create(self.device, self.rate, self.N, self.hop, self.n_mels, float(low_freq),
+                                       float(high_freq), self.preemphasis, self.scale, FBANK_WINDOWS[window],
+                                       self.flags, C.byref(self._h)))
+        pp, k, t = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        p = [C.c_void_p() for _ in range(5)]
+        _check(lib().mp3g_fbank_info(self._h, C.byref(pp), C.byref(k), *[C.byref(q) for q in p], C.byref(t)))
+        self.P, self.K, self.tile_frames = pp.value, k.value, t.value
+
+        def view(q, ctype, shape):  # a view of the library's table: valid while this object lives
+            return np.ctypeslib.as_array(C.cast(q, C.POINTER(ctype)), shape=shape)
+        self.cw = view(p[0], C.c_float, (self.K, self.N))
+        self.sw = view(p[1], C.c_float, (self.K, self.N))
+        self.wm = view(p[2], C.c_float, (self.n_mels, self.K))
+        self.support = view(p[3], C.c_uint32, (self.n_mels, 2))
+        self.w = view(p[4], C.c_float, (self.N,))
+
+    def frames(self, T):
+        """The frames a row of T samples has (mp3g_fbank_frames)."""
+        return int(lib().mp3g_fbank_frames(self._h, int(T)))
+
+    def host(self, x, n_frames=None, mel_stride=None):
+        """The reference on the CPU (mp3g_fbank_host): features [n_frames,
+        n_mels] of the float32 row x (n_frames: all by default); with a
+        mel_stride the full [n_frames, mel_stride] buffer, zeros where nothing
+        is written."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = self.frames(len(x)) if n_frames is None else int(n_frames)
+        stride = self.n_mels if mel_stride is None else int(mel_stride)
+        out = np.zeros((max(n, 0), max(stride, 0)), np.float32)
+        _check(lib().mp3g_fbank_host(self._h, _ptr(x) if len(x) else None, len(x), n, _ptr(out) if out.size else None,
+                                     stride))
+        return out
+
+    def execute(self, d_src, d_out=None, stream=None):
+        """The device call (mp3g_fbank_execute): d_src float32 [B, C, T] (C = 1
+        or 2) or [B, T], contiguous on this object's device; d_out float32
+        [B, C, F, S] or [B, F, S] with F <= frames(T) and S >= n_mels (made here
+        when None: every frame, S = n_mels).  Writes the n_mels features of each
+        of the F frames, nothing else.  One launch, asynchronous on `stream` (a
+        hipStream_t; None = the current torch stream).  Returns d_out."""
+        import torch
+        if d_src.dtype != torch.float32 or not d_src.is_contiguous() or d_src.dim() not in (2, 3) or not d_src.is_cuda:
+            raise ValueError("FBank.execute: a contiguous float32 device tensor [B, C, T] or [B, T]")
+        B, T = int(d_src.shape[0]), int(d_src.shape[-1])
+        planes = int(d_src.shape[1]) if d_src.dim() == 3 else 1
+        lead = (B, planes) if d_src.dim() == 3 else (B,)
+        if d_out is None:
+            d_out = torch.empty(lead + (self.frames(T), self.n_mels), dtype=torch.float32, device=d_src.device)
+        if (d_out.dtype != torch.float32 or not d_out.is_contiguous() or not d_out.is_cuda
+                or d_out.dim() != len(lead) + 2 or tuple(d_out.shape[:-2]) != lead):
+            raise ValueError("FBank.execute: d_out is a contiguous float32 device tensor [B, (C,) F, S]")
+        if stream is None:
+            stream = torch.cuda.current_stream(d_src.device).cuda_stream
+        _check(lib().mp3g_fbank_execute(self._h, C.c_void_p(d_src.data_ptr()) if d_src.numel() else None, B, planes, T,
+                                        C.c_void_p(d_out.data_ptr()) if d_out.numel() else None,
+                                        int(d_out.shape[-2]), int(d_out.shape[-1]), C.c_void_p(stream) if stream else None))
+        return d_out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.cw = self.sw = self.wm = self.support = self.w = None
+            lib().mp3g_fbank_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_length_ms=25.0, frame_shift_ms=10.0,
+                                n_mels=80, low_freq=20.0, high_freq=0.0, preemphasis=0.97, remove_dc=True,
+                                window="povey", snip_edges=True, scale=32768.0, n_frames=None, mode=MODE_EXACT,
+                                out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0, device=0):
+    """decode_windows_resampled_tensor followed by FBank.execute on the same
+    torch stream: Kaldi's filter-bank features of each stream's window
+    [starts[k], starts[k] + n_samples) at `rate`, zero padding included.
+    F = n_frames, by default every frame a row of n_samples has.
+
+    Returns (features, frame_lengths, end_status, rates): features [B, F,
+    n_mels] (OUT_F32_MONO) or [B, 2, F, n_mels] (OUT_F32_PLANAR) on cuda:device,
+    equal to FBank.host on the rows of decode_windows_resampled_tensor bit for
+    bit; frame_lengths int64[B], the frames that lie wholly inside each stream's
+    valid samples: clamp((len - N) // hop + 1, 0, F) with snip_edges, else
+    min(F, (len + hop // 2) // hop).  A frameless stream's rows are all
+    logf(2^-23)."""
+    import torch
+    fb = FBank(rate, frame_length_ms, frame_shift_ms, n_mels, low_freq, high_freq, preemphasis, remove_dc, window,
+               snip_edges, scale, device=device)
+    try:
+        T = int(n_samples)
+        avail = fb.frames(T)
+        F = avail if n_frames is None else int(n_frames)
+        if F < 0 or F > avail:
+            raise Mp3gError(1, "more frames than a row of n_samples has")
+        batch, lengths, end_status, rates = decode_windows_resampled_tensor(
+            datas, starts, T, rate, mode=mode, out_format=out_format, gapless=gapless, quality=quality,
+            n_threads=n_threads, device=device)
+        feats = torch.empty(tuple(batch.shape[:-1]) + (F, fb.n_mels), dtype=torch.float32, device=batch.device)
+        fb.execute(batch, feats)
+        torch.cuda.current_stream(feats.device).synchronize()
+        if snip_edges:
+            flen = np.clip((lengths - fb.N) // fb.hop + 1, 0, F)
+        else:
+            flen = np.minimum(F, (lengths + fb.hop // 2) // fb.hop)
+    finally:
+        fb.close()
+    return feats, flen, end_status, rates
 
 
 def _host_buffer(out, want_int16, want_float32=False):

@@ -53,7 +53,8 @@ extern "C" {
  *    mp3g_scan_windows, mp3g_scan_window_rows, mp3g_plan_create_windows and
  *    mp3g_plan_execute_windows; sample-rate conversion of decoded rows --
  *    mp3g_resampler_*, mp3g_resample_host, mp3g_resample_rows and
- *    mp3g_stream_rates; log-mel features of decoded rows -- mp3g_logmel_*.) */
+ *    mp3g_stream_rates; log-mel features of decoded rows -- mp3g_logmel_*;
+ *    Kaldi filter-bank features of decoded rows -- mp3g_fbank_*.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -697,6 +698,107 @@ int mp3g_logmel_execute(const mp3g_logmel* lm, const float* d_src, uint32_t n_ro
                         float* d_out, uint32_t n_frames, uint32_t frame_stride, void* hip_stream);
 /* Test hook: y[i] = mp3g_log10f(x[i]) (normal positive finite x). */
 void mp3g_logmel_log10f(const float* x, uint64_t n, float* y);
+
+/* ---- Kaldi filter-bank features of decoded rows ------------------------------
+ * The other family of speech front ends: Kaldi's compute-fbank-feats (what
+ * torchaudio.compliance.kaldi.fbank restates), the input of the Conformer /
+ * Zipformer, Paraformer, AST and speaker-embedding models.  It differs from the
+ * log-mel features above in more than parameters: every frame is processed on
+ * its own before the window (DC removal, pre-emphasis), the FFT length is the
+ * window rounded up to a power of two, the mel bank is unnormalised triangles
+ * in the 1127 ln(1 + f / 700) domain, the logarithm is natural and floored at
+ * float32 epsilon, and the features are time-major.  Every feature is a fixed
+ * sequence of float32 operations, so the device call equals mp3g_fbank_host bit
+ * for bit.  No reference counterpart (go-mp3 delivers samples).
+ *
+ * Parameters.  rate > 0; the window length N in samples, any integer in [16,
+ * 1024]; 1 <= hop <= N; n_mels in 1..128; low_freq and high_freq with Kaldi's
+ * meaning (high_freq <= 0 means rate / 2 + high_freq; then 0 <= low < high <=
+ * rate / 2); preemph in [0, 1]; scale finite and > 0 (Kaldi models read
+ * int16-range samples: 32768; the product with a sample is exact when scale is
+ * a power of two); window one of MP3G_FBANK_WINDOW_*; flags MP3G_FBANK_REMOVE_DC
+ * and MP3G_FBANK_SNIP_EDGES.  P is the smallest power of two >= N (P <= 1024)
+ * and K = P / 2 bins: the Nyquist bin carries no weight in Kaldi's bank and is
+ * not computed.  A value that is not positive, an unknown flag or window, a
+ * violated relation or a non-finite parameter is MP3G_ERR_INVALID_ARGUMENT; an N
+ * or n_mels outside the supported range MP3G_ERR_UNSUPPORTED; both before any
+ * device call, with *out = NULL.
+ * Not offered: dither (random, so not reproducible), the energy column, VTLN,
+ * subtract_mean, and magnitude (non-power) or non-log output.
+ *
+ * Framing.  One row is a float32 signal x[0, T) (a plane of the dense batch,
+ * its zero padding included).  A row with T < N has no frames, in both modes.
+ * With MP3G_FBANK_SNIP_EDGES there are F = 1 + (T - N) / hop frames and frame f
+ * starts at f hop.  Without it F = (T + hop / 2) / hop (integer divisions),
+ * frame f starts at f hop + hop / 2 - N / 2 and reads xr, x reflected Kaldi's
+ * way: xr[j] = x[-j - 1] for j < 0 and x[2 T - 1 - j] for j >= T (the edge
+ * sample is repeated, unlike the log-mel reflection).
+ *
+ * Tables, computed in float64 and rounded once to float32:
+ *   w[n], n = 0 .. N-1, a = 2 pi n / (N - 1): POVEY (0.5 - 0.5 cos a)^0.85,
+ *   HAMMING 0.54 - 0.46 cos a, HANNING 0.5 - 0.5 cos a, RECTANGULAR 1
+ *   Cw[k][n] = w[n] cos(2 pi ((k n) mod P) / P),  Sw[k][n] = -w[n] sin(..),  k < K
+ *   Wm[m][k]: Kaldi's get_mel_banks without VTLN -- mel(f) = 1127 ln(1 + f / 700),
+ *   d = (mel(high) - mel(low)) / (n_mels + 1), left = mel(low) + m d, centre =
+ *   left + d, right = centre + d, mk = mel(k rate / P), Wm = max(0, min((mk -
+ *   left) / d, (right - mk) / d)); no area normalisation; filter m's non-zero
+ *   entries are k in [lo_m, hi_m] (lo > hi: an empty filter)
+ *   rN = float32(1 / N)
+ *
+ * Features, all float32, start = the frame's first index:
+ *   s[n] = scale * xr[start + n]                            n = 0 .. N-1
+ *   sum = +0; sum = fmaf(s[n], 1.0f, sum), n ascending; mean = sum * rN
+ *   d[n] = fmaf(mean, -1.0f, s[n])          (MP3G_FBANK_REMOVE_DC; else d = s)
+ *   e[0] = fmaf(-preemph, d[0], d[0]);  e[n] = fmaf(-preemph, d[n-1], d[n])
+ *   re = im = +0;  for n = 0 .. N-1: re = fmaf(Cw[k][n], e[n], re), im alike
+ *   p[k] = fmaf(re, re, im * im)                 (the product rounded first)
+ *   mel = +0;  for k = lo_m .. hi_m: mel = fmaf(Wm[m][k], p[k], mel)
+ *   y[f][m] = mp3g_logf(max(mel, 0x1p-23f))
+ * -- each sum ONE FMA chain in ascending order; the order is part of the
+ * contract.  preemph = 0 still runs the e step (fmaf(-0, d, d) is d for finite
+ * d).  mp3g_logf (go-mp3_amd/csrc/fbank_log.h) is built like mp3g_log10f from
+ * integer operations and explicit FMAs only and compiled by host and device
+ * alike; it is within one ulp of the float32 nearest to ln (faithful).
+ *
+ * Domain: finite samples with |scale x| <= 2^20; float32 subnormals are kept.
+ * Output: float [row][plane][n_frames][mel_stride], mel_stride >= n_mels: time-
+ * major, Kaldi's layout.  n_mels features are written per frame, nothing else. */
+#define MP3G_FBANK_REMOVE_DC 1u
+#define MP3G_FBANK_SNIP_EDGES 2u
+#define MP3G_FBANK_WINDOW_POVEY 0
+#define MP3G_FBANK_WINDOW_HAMMING 1
+#define MP3G_FBANK_WINDOW_HANNING 2
+#define MP3G_FBANK_WINDOW_RECTANGULAR 3
+#define MP3G_FBANK_MIN_WINDOW 16
+#define MP3G_FBANK_MAX_WINDOW 1024
+#define MP3G_FBANK_MAX_MELS 128
+typedef struct mp3g_fbank mp3g_fbank;
+/* Builds the tables; device >= 0 also uploads them to that device (once),
+ * device = -1 makes a host-only object. */
+int mp3g_fbank_create(int device, int rate, int N, int hop, int n_mels, double low_freq, double high_freq,
+                      double preemph, double scale, int window, uint32_t flags, mp3g_fbank** out);
+void mp3g_fbank_free(mp3g_fbank* fb);
+/* P, K, the host tables Cw and Sw float [K][N] and Wm float [n_mels][K], the
+ * supports uint32 [n_mels][2] = lo_m, hi_m, the window w float [N] -- all owned
+ * by the object -- and the frames a workgroup of the device call produces (any
+ * may be NULL). */
+int mp3g_fbank_info(const mp3g_fbank* fb, uint32_t* P, uint32_t* K, const float** cw, const float** sw,
+                    const float** wm, const uint32_t** support, const float** w, uint32_t* tile_frames);
+/* The frames a row of T samples has (0: none, or T >= 2^62). */
+uint64_t mp3g_fbank_frames(const mp3g_fbank* fb, uint64_t T);
+/* The definition above in plain C++ (the reference the device call equals):
+ * out[f * mel_stride + m] for f < n_frames <= mp3g_fbank_frames, m < n_mels. */
+int mp3g_fbank_host(const mp3g_fbank* fb, const float* x, uint64_t T, uint64_t n_frames, float* out,
+                    uint64_t mel_stride);
+/* d_src: float [n_rows][n_planes][T]; d_out: float [n_rows][n_planes][n_frames]
+ * [mel_stride].  Both are device pointers and the launch shape depends on none
+ * of their contents: one launch, asynchronous on hip_stream and graph-
+ * capturable.  T < 2^31; n_frames <= mp3g_fbank_frames(fb, T), mel_stride >=
+ * n_mels. */
+int mp3g_fbank_execute(const mp3g_fbank* fb, const float* d_src, uint32_t n_rows, uint32_t n_planes, uint32_t T,
+                       float* d_out, uint32_t n_frames, uint32_t mel_stride, void* hip_stream);
+/* Test hook: y[i] = mp3g_logf(x[i]) (normal positive finite x). */
+void mp3g_fbank_logf(const float* x, uint64_t n, float* y);
 
 /* ---- decoder: mp3.NewDecoder / io.Reader / io.Seeker (decode.go:27-388) ----
  * Scans on the host with read-ahead (headers, side info, reservoir) and
