@@ -86,17 +86,23 @@ __device__ __forceinline__ f2 bcast(float v) { return (f2){v, v}; }
 // pretab[22] (frame.go:39) packed 2 bits per band: no per-lane table load
 __device__ __forceinline__ int kPretab(int sfb) { return (int)((0x2fe95400000ull >> (2 * sfb)) & 3u); }
 // The X ring, column-major: ring[ch][m][u] = X_u[m], the value m (in
-// dct32::kPosOfM order) of time slot u.  Slots 1..15 hold the previous
-// granule's last 15 slots (slot 0 is unused), 16..33 the current granule; the
-// window of slot ss reads slots 16+ss-j, j = 0..15, so 15 history slots
-// suffice (the 16th V block of Frame.vVec is never read again).
-//  * every operand pair of the window is two consecutive slots of one column:
-//    (16+v, 17+v), v even, is one 8-B aligned ds_read_b64, (15+v, 16+v) one
-//    ds_read2_b32;
+// dct32::kPosOfM order) of time slot u.  By virtual slot: 1..15 hold the
+// previous granule's last 15 slots (slot 0 is unused), 16..33 the current
+// granule; the window of slot ss reads slots 16+ss-j, j = 0..15, so 15 history
+// slots suffice (the 16th V block of Frame.vVec is never read again).  Where a
+// virtual slot lies in the column alternates between two layouts (rphys
+// below), so that the history is handed from granule to granule in place: no
+// history shift (it was eight 8-B reads and writes per lane and granule, a
+// dependent LDS round trip and a wave_sync).
+//  * every operand pair of the window is two consecutive virtual slots of one
+//    column: (16+v, 17+v), v even, is one 8-B aligned ds_read_b64, (15+v,
+//    16+v) one ds_read2_b32 -- but for the two pairs that straddle the parts
+//    of a column that the layouts place differently, (18, 19) and (15, 16):
+//    two ds_read_b32 each;
 //  * 34 dwords per column (34 = 2 mod 32): the columns the 32 lanes of a
 //    channel read start in distinct even banks (conflict-free b64 reads);
-//  * the matrixing lane of slot u reads and writes its slot across the 32
-//    columns: consecutive lanes hit consecutive dwords;
+//  * the matrixing lane u reads and writes one of the 18 written positions
+//    (rcur + u) across the 32 columns: consecutive lanes hit consecutive dwords;
 //  * 2 x 32 x 34 x 4 = 8,704 B per wave, which with the raw coefficients in
 //    registers (no LDS copy) brings an 8-wave workgroup to 75 KB: 2
 //    workgroups = 16 waves per CU.
@@ -108,6 +114,75 @@ constexpr int kHist = 16;
 #endif
 constexpr int kSlots = kHist + 18;
 static_assert(kSlots == kFastRingSlots, "FastTables::sinfo indexes the staged ring");
+// Two layouts of the 34-slot column, alternating from one stereo granule to
+// the next, so that the history is never moved.  A window operand is named by
+// its virtual slot z (as in granule_synth.hip): z = 1..15 the history (slots
+// 3..17 of the previous granule), z = 16 + j the current granule's slot j.
+// Position in the column:
+//   layout E (P = 0): z -- history in 1..15, current in 16..33 (the only
+//                     layout of the exact kernels and of a chunk's entry);
+//   layout O (P = 1): history at 18 + z = 19..33, where E left its slots
+//                     3..17; current j = 0, 1, 2 at 16, 17, 18 and j = 3..17
+//                     at j - 2 = 1..15, where E expects its history.
+// Both hand-overs are identities, and the positions a granule writes (E:
+// 16..33, O: 1..18) hold nothing it still reads.  Position 0 is never used.
+__device__ __forceinline__ constexpr int rphys(int P, int z) { return !P ? z : z <= 15 ? 18 + z : z <= 18 ? z : z - 18; }
+// The same map as displacements, which is how the kernel addresses the ring --
+// one code path for both layouts, the layout in two per-granule pointers: a
+// history slot (z <= 15) lies 18 P positions above z, a current slot from
+// j = 3 on (z >= 19) 18 P below, and the current slots j = 0, 1, 2 (z = 16,
+// 17, 18) do not move.  18 positions are 72 B: 8-B aligned pairs stay aligned.
+__device__ __forceinline__ constexpr int rregion(int z) { return z <= 15 ? 0 : z <= 18 ? 1 : 2; }
+__device__ __forceinline__ constexpr int rshift(int P, int z) { return rregion(z) == 0 ? 18 * P : rregion(z) == 2 ? -18 * P : 0; }
+// the first of the 18 positions a granule writes (they are contiguous): where
+// the short-block path stages raw lines and where the matrixing lanes sit
+__device__ __forceinline__ constexpr int rcur(int P) { return P ? 1 : kHist; }
+namespace ring_map {
+constexpr bool bijective(int P) {
+  unsigned long long seen = 0;
+  for (int z = 1; z <= 33; z++) {
+    const int p = rphys(P, z);
+    if (p < 1 || p > 33 || ((seen >> p) & 1)) return false;
+    seen |= 1ull << p;
+  }
+  return true;
+}
+// this layout's slots 3..17 are the other layout's history 1..15, in place
+constexpr bool hands_over(int P) {
+  for (int z = 1; z <= 15; z++)
+    if (rphys(P, 18 + z) != rphys(!P, z)) return false;
+  return true;
+}
+// the current set is the 18 positions from rcur(P) on
+constexpr bool cur_contiguous(int P) {
+  for (int j = 0; j < 18; j++)
+    if (rphys(P, 16 + j) < rcur(P) || rphys(P, 16 + j) >= rcur(P) + 18) return false;
+  return true;
+}
+// the window's A pairs (16 + v, 17 + v), v even: one aligned 8-B read each,
+// but for (18, 19) in layout O, which sits at (18, 1)
+constexpr bool a_pairs_aligned(int P) {
+  for (int v = -14; v <= 16; v += 2) {
+    const int a = rphys(P, 16 + v), b = rphys(P, 17 + v);
+    if (P && v == 2) {
+      if (a != 18 || b != 1) return false;
+    } else if ((a & 1) || b != a + 1) {
+      return false;
+    }
+  }
+  return true;
+}
+constexpr bool shifts_agree(int P) {
+  for (int z = 1; z <= 33; z++)
+    if (rphys(P, z) != z + rshift(P, z)) return false;
+  return true;
+}
+static_assert(shifts_agree(0) && shifts_agree(1), "rshift is rphys as a displacement");
+static_assert(bijective(0) && bijective(1), "a layout maps the virtual slots 1..33 onto the positions 1..33");
+static_assert(hands_over(0) && hands_over(1), "the history changes layout without moving");
+static_assert(cur_contiguous(0) && cur_contiguous(1), "rcur: the written positions");
+static_assert(a_pairs_aligned(0) && a_pairs_aligned(1), "8-B aligned A pairs");
+}  // namespace ring_map
 #ifndef MP3G_FAST_DWIN_STRIDE
 #define MP3G_FAST_DWIN_STRIDE 20
 #endif
@@ -146,10 +221,12 @@ struct __align__(16) SharedSmem {
 // stay <= 64 x 1280 B (gfx950 LDS allocation granule) for 2 workgroups
 // (16 waves) per CU.
 struct __align__(16) WaveSmem {
-  // the current granule's slots of a column (16..33) first receive S (the
-  // IMDCT output of subband k = column, one value per slot) and the matrixing
-  // turns them into X in place; before that they stage the raw coefficients
-  // of short-block granules (reorder gather) and the intensity-stereo pass
+  // the current granule's slots of a column (positions 16..33 in layout E,
+  // 1..18 in layout O: rphys) first receive S (the IMDCT output of subband k =
+  // column, one value per slot) and the matrixing turns them into X in place;
+  // before that the first nine of them stage the raw coefficients of
+  // short-block granules (reorder gather).  The other 15 used positions hold
+  // the history, which no granule moves: the next one takes the other layout.
   float ring[2][32][kSlots];
   // the current granule's descriptor, for the paths that index it per line
   // (16-B aligned: the channels' first 8 bytes are one 8-B read each).  The
@@ -1159,7 +1236,8 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
   // PCM stores are issued for replayed granules too, through a resource with
   // no records)
   // the window sums of output k: acc2[p] = slots (2p, 2p + 1), times 32767
-  auto window_acc = [&](f2 (&acc2)[9]) {
+  // (par: the ring layout of the granule, wave-uniform)
+  auto window_acc = [&](uint32_t par, f2 (&acc2)[9]) {
     float dw[16];
     {
       const float4* d4 = reinterpret_cast<const float4*>(&sh.dwin[k][0]);
@@ -1176,15 +1254,25 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     // column a of rows (v, v+1) and tap 2t+1 column b of rows (v-1, v),
     // v = 2p - 2t: every operand pair is two rows of one column, i.e. one
     // ds_read2_b32 that lands as the packed operand, and each feeds up to 8
-    // accumulator pairs.
-    const f2* RA = reinterpret_cast<const f2*>(&s.ring[ch][pa][0]);
+    // accumulator pairs.  Rows by virtual slot z (rshift): the history from a
+    // pointer 18 par above the column, the current slots from j = 3 on from
+    // one 18 par below it, z = 16, 17, 18 from the column itself -- the same
+    // instructions in both layouts.  A pair inside one region is one read (A:
+    // 8-B aligned, a ds_read_b64; B: a ds_read2_b32); the two pairs that
+    // straddle regions, A's (18, 19) and B's (15, 16), are two ds_read_b32.
+    const float* RA = &s.ring[ch][pa][0];
     const float* RB = &s.ring[ch][pb][0];
+    const int d = par ? 18 : 0;
+    const float* const RAr[3] = {RA + d, RA, RA - d};
+    const float* const RBr[3] = {RB + d, RB, RB - d};
 #pragma unroll
     for (int p = 0; p < 9; p++) acc2[p] = bcast(0.0f);
 #pragma unroll
     for (int v = -14; v <= 16; v += 2) {
-      const f2 A = RA[(kHist + v) / 2];  // slots (16+v, 17+v): 8-B aligned
-      const f2 B = {RB[kHist + v - 1], RB[kHist + v]};
+      const int za = kHist + v, zb = kHist + v - 1;
+      const f2 A = rregion(za) == rregion(za + 1) ? *reinterpret_cast<const f2*>(RAr[rregion(za)] + za)
+                                                  : (f2){RAr[rregion(za)][za], RAr[rregion(za + 1)][za + 1]};
+      const f2 B = {RBr[rregion(zb)][zb], RBr[rregion(zb + 1)][zb + 1]};
 #pragma unroll
       for (int t = 0; t < 8; t++) {
         const int p = v / 2 + t;
@@ -1200,7 +1288,8 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
   if constexpr (kFmt == (int)MP3G_OUT_F32_PLANAR)
     geom = StreamGeom{(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)cd.stream_first),
                       (uint32_t)__builtin_amdgcn_readfirstlane(cd.stream_n)};
-  auto window_store = [&](uint32_t g, bool out, int nch) {
+  // (par: the ring layout of this granule, wave-uniform)
+  auto window_store = [&](uint32_t g, bool out, int nch, uint32_t par) {
     if constexpr (kFmt != (int)MP3G_OUT_S16) {
       // the format's registers (replayed granules: zeros to no records, the
       // same number of stores; zeroed in the else, as `= {}` in front of the
@@ -1208,7 +1297,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       typename PcmRegs<kFmt>::type pr;
       if (out) {
         f2 acc2[9];
-        window_acc(acc2);
+        window_acc(par, acc2);
         pack_granule<kFmt>(acc2, nch, pr);
       } else {
 #pragma unroll
@@ -1221,7 +1310,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     // whatever it holds to no records) and the stores are written out here
     if (out) {
       f2 acc2[9];
-      window_acc(acc2);
+      window_acc(par, acc2);
       pack_pcm(acc2, nch, pk);
       // stored right away: a store's data registers are free again once it
       // has issued (no s_waitcnt before their reuse on gfx950), and the loads
@@ -1254,7 +1343,15 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
   // granule instead of recomputing the level)
   const uint32_t t3 = end - (span3 >> 2), t2 = end - (span2 >> 2), t1 = end - (span >> 2);
   if (MP3G_FAST_PRIO) __builtin_amdgcn_s_setprio(3);
+  // the ring's state, wave-uniform.  Bit 0: the layout (rphys) -- E at the
+  // chunk's entry (the entry history above), flipped by every granule that
+  // leaves a history.  Bit 1: channel 1's frozen history lies in the history
+  // places of both layouts (a run of mono granules, see the hand-over below).
+  uint32_t lay = 0;
   for (uint32_t g = w; g < end; g++) {
+    const uint32_t par = lay & 1u;
+    // the first of the 18 positions this granule writes (16 or 1)
+    const int cur = par ? rcur(1) : rcur(0);
     if (MP3G_FAST_PRIO) {
       if (g == t1) __builtin_amdgcn_s_setprio(0);
       else if (g == t2) __builtin_amdgcn_s_setprio(1);
@@ -1378,15 +1475,19 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       int nsfs = 0;  // short bands whose first line lies below count1 (frame.go:229-255 loop bound)
 #pragma unroll
       for (int b = 0; b < 13; b++) nsfs += 3 * (int)g_fast.sfb_short[combo][b] < count1;
-      // reorder gather: the channel's raw lines staged in the current slots of
-      // the ring, lane (ch, sb) writing its 9 dwords to column sb
-      {
-        uint32_t* col = reinterpret_cast<uint32_t*>(&s.ring[ch][k][kHist]);
+      // reorder gather: the channel's raw lines staged in the positions this
+      // granule writes (from `cur` on: no history of its layout there), lane
+      // (ch, sb) writing its 9 dwords to column sb.  The lanes of an absent
+      // channel write nothing -- in a run of mono granules channel 1's column
+      // holds its history in both layouts' places -- and gather whatever lies
+      // there: like everything they compute, it is never used.
+      if (act) {
+        uint32_t* col = reinterpret_cast<uint32_t*>(&s.ring[ch][k][0]) + cur;
 #pragma unroll
         for (int q = 0; q < 9; q++) col[q] = cw[q];
       }
       wave_sync();
-      const int16_t* rch = reinterpret_cast<const int16_t*>(&s.ring[ch][0][kHist]);
+      const int16_t* rch = reinterpret_cast<const int16_t*>(&s.ring[ch][0][0] + cur);
       // line info through a buffer resource (SGPR base, 32-bit lane offset) and
       // the lane's first line recomputed here: nothing of this rare path stays
       // live (in VGPRs) across the granule loop.  Short, non-mixed blocks in
@@ -1437,6 +1538,13 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
           x[j] = self(process, requant_fast(xi, s.expo[eidx]), (float)xi);
         }
       }
+      // the line info words are all in (this path has waited for them): said
+      // once, so that no load of this rare path counts as pending anywhere
+      // later in the granule -- the wait-count pass then puts a vmcnt(0) in
+      // front of the first reuse of such a register, on paths every granule
+      // takes (seen in the frozen-channel overlap: a wait for the previous
+      // granule's PCM stores)
+      settle_vmem();
       wave_sync();  // staged lines read before the slots are reused
     }
     stamp(1);
@@ -1649,24 +1757,39 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     //      the 32 distinct values X of V = synthNWin * S with an in-lane fast
     //      DCT-II-32 on float pairs (dct32.h), in place ----
     if (need_v && act) {
+      // (eight 8-B writes; the pair (o[2], o[3]) straddles the fixed slots and
+      // those that move with the layout: two 4-B writes)
+      float* col = &s.ring[ch][k][0];
+      float* const colr[3] = {nullptr, col, col - (par ? 18 : 0)};
 #pragma unroll
-      for (int j = 0; j < 18; j++) s.ring[ch][k][kHist + j] = o[j];
+      for (int j = 0; j < 18; j += 2) {
+        const int z = kHist + j;
+        if (rregion(z) == rregion(z + 1)) {
+          *reinterpret_cast<f2*>(colr[rregion(z)] + z) = (f2){o[j], o[j + 1]};
+        } else {
+          colr[rregion(z)][z] = o[j];
+          colr[rregion(z + 1)][z + 1] = o[j + 1];
+        }
+      }
     }
     wave_sync();
 #if MP3G_HOT_CHECK
     // the second test (rare) on S in the ring: the granule's zone is redone
     // in the reference's order after the pass (a granule whose V feeds no
     // output needs no zone)
-    if (hot1 && need_v && slot_sums_hot(s.ring, nch)) {
+    if (hot1 && need_v && slot_sums_hot(s.ring, nch, cur)) {
       record_hot(s, nz, gran, g, out_first, end);
       if constexpr (kHotCount) n_flagged++;
     }
 #endif
     stamp(4);
     {
-      const int slot = lane & 31;  // lane = (ch, slot), slots 0..17
+      // lane = (ch, slot), slots 0..17: the lane takes position cur + slot of
+      // the written set (any one-to-one assignment does: the transform is
+      // in place; this one keeps consecutive lanes on consecutive dwords)
+      const int slot = lane & 31;
       if (need_v && act && slot < 18) {
-        float* colu = &s.ring[ch][0][kHist + slot];  // S[k] / X at colu[kSlots * k]
+        float* colu = &s.ring[ch][0][0] + cur + slot;  // S[k] / X at colu[kSlots * k]
         dct32::f2 sp[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) sp[q] = (dct32::f2){colu[kSlots * 2 * q], colu[kSlots * (2 * q + 1)]};
@@ -1687,26 +1810,53 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     dv = dvn;
     dvn = pdw;
 
-    window_store(g, out, nch);
-    wave_sync();  // ring reads done
+    window_store(g, out, nch, par);
+    // ring reads done: the one ordering point between this granule's window
+    // (other lanes' reads of these columns) and the next granule's writes to
+    // them -- staged lines or S rows
+    wave_sync();
     stamp(6);
 
-    // ---- history shift (channels this granule touched): lane = (c, column),
-    //      slots 18..33 -> 0..15 as 8-B moves; not after a replayed granule
-    //      whose V feeds nothing (its slots hold no X; the next granule is a
-    //      replay too and rewrites the history before any window reads it) ----
-    if (ch < nch && need_v) {
-      f2* col = reinterpret_cast<f2*>(&s.ring[ch][k][0]);
+    // ---- history hand-over; none after a replayed granule whose V feeds
+    //      nothing (its slots hold no X; the next granule is a replay too and
+    //      rewrites the history before any window reads it).  Nothing moves:
+    //      the next granule takes the other layout, whose history this
+    //      granule's slots 3..17 are where they lie.  A mono granule leaves
+    //      channel 1's column alone (frame.go Decode touches ch < nch), so
+    //      the first of a run copies channel 1's frozen history to the other
+    //      layout's history place, lane = column (E -> O: positions 0..15 ->
+    //      18..33 as 8-B moves, O -> E: 18..33 -> 0..15; positions 0 and 18
+    //      ride along, neither holds anything then).  From there on the
+    //      column serves both layouts, until a stereo granule writes it.
+    //      (A stereo granule whose V feeds nothing keeps the layout, but it
+    //      may have staged raw lines over the other layout's place: bit 1
+    //      goes with every stereo granule.) ----
+    if (nch == 2) {
+      lay = need_v ? par ^ 1u : par;
+    } else if (need_v) {
+      if (!(lay & 2u)) {
+        if (ch == 1) {
+          f2* col2 = reinterpret_cast<f2*>(&s.ring[1][k][0]);
+          if (par) {
 #pragma unroll
-      for (int q = 0; q < 8; q++) col[q] = col[9 + q];
+            for (int q = 0; q < 8; q++) col2[q] = col2[9 + q];
+          } else {
+#pragma unroll
+            for (int q = 0; q < 8; q++) col2[9 + q] = col2[q];
+          }
+        }
+        wave_sync();
+      }
+      lay = (par ^ 1u) | 2u;
     }
-    wave_sync();
     stamp(7);
   }
   if constexpr (kStamp) rt[2] = __builtin_amdgcn_s_memrealtime();
 
-  // Frame.store / vVec after the chunk's last granule (frame.go:48-49)
-  auto export_state = [&](const f2 (&st)[9]) {
+  // Frame.store / vVec after the chunk's last granule (frame.go:48-49); Pn:
+  // the layout the next granule would have used, whose history the last 15 V
+  // blocks are
+  auto export_state = [&](const f2 (&st)[9], uint32_t Pn) {
     if (!(cd.flags & kChunkStateOut)) return;
     mp3g_state* so = state_out + cd.stream;
     const int c = lane_fresh() >> 5, kk = lane_fresh() & 31;
@@ -1718,10 +1868,12 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     }
     for (int e = lane_fresh(); e < 2 * 1024; e += kLanes) {
       const int cc = e >> 10, blk = (e >> 6) & 15, i = e & 63;
-      so->vvec[cc][64 * blk + i] = blk < 15 ? v_from_x(&s.ring[cc][0][kHist - 1 - blk], i) : 0.0f;
+      const int z = kHist - 1 - blk;  // (blk < 15: a history slot)
+      so->vvec[cc][64 * blk + i] = blk < 15 ? v_from_x(&s.ring[cc][0][0] + (Pn ? 18 + z : z), i) : 0.0f;
     }
   };
-  export_state(stp);
+  static_assert(rphys(1, 1) == 19 && rphys(1, 15) == 33 && rphys(0, 15) == 15, "export_state's history positions");
+  export_state(stp, lay & 1u);
 
   // ---- hot zones (rare): redo their granules in the reference's order from
   //      their replay start (exact entry state) and overwrite their PCM; a
@@ -1828,7 +1980,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       }
       done = gz;
     }
-    if (done >= end) export_state(zst);
+    if (done >= end) export_state(zst, 0u);  // (the zone pass keeps layout E: init_state, exact_granule)
     // (rare: one vector atomic per counter from lane 0 of a chunk with zones)
     if (kHotCount && hot_count && lane_fresh() == 0) {
       atomicAdd(hot_count + 0, n_out);
