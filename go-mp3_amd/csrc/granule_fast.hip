@@ -320,8 +320,18 @@ __device__ __forceinline__ int count1_lim(const mp3g_granule* gran, uint32_t g, 
 
 // Replay start of a chunk (same decision as v2::plan_prologue, with wave
 // ballots instead of a workgroup scan).
+// ch1_always (the fast pass): go back to the last two stereo granules behind
+// a mono run even when the chunk itself has no stereo granule and exports no
+// state.  Channel 1 does not matter to such a chunk's PCM, but whether the
+// stereo granule in front of the run is hot does: its zone runs across the
+// whole run (zone_end), a serial decode rewrites the run's granules in the
+// reference's order, and a chunk that never met that granule kept the fast
+// transforms' output there -- within 1 LSB, but not the same bytes as the
+// serial decode.  The price: a chunk that starts r granules into a mono run
+// replays r + 2 granules or more instead of 2.  The exact kernels (and so the
+// zone pieces) need no such replay: their output does not depend on it.
 __device__ void prologue(const ChunkDesc& cd, const mp3g_granule* gran, uint64_t* w_out, int init_in[2],
-                         int lane) {
+                         int lane, bool ch1_always = false) {
   const uint64_t c0 = cd.out_first, s0 = cd.stream_first;
   const bool have_in = cd.flags & kChunkStateIn;
   if (c0 == s0) {
@@ -337,8 +347,9 @@ __device__ void prologue(const ChunkDesc& cd, const mp3g_granule* gran, uint64_t
     init_in[0] = init_in[1] = (start0 == s0) && have_in;
     return;
   }
-  int any = 0;
-  for (uint32_t k = lane; k < cd.n_out; k += kLanes) any |= hdr_nch(gran[c0 + k].header) == 2;
+  int any = ch1_always;
+  if (!ch1_always)
+    for (uint32_t k = lane; k < cd.n_out; k += kLanes) any |= hdr_nch(gran[c0 + k].header) == 2;
   const bool need1 = __ballot(any) != 0 || (cd.flags & kChunkStateOut);
   uint64_t start1 = c0;
   bool ch1_from_in = false;
@@ -1169,7 +1180,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
 
   uint64_t w64;
   int init_in[2];
-  prologue(cd, gran, &w64, init_in, lane);
+  prologue(cd, gran, &w64, init_in, lane, true);
   // loop state as wave-uniform 32-bit scalars (plans are limited to < 2^32
   // granules): keeps it in SGPRs, so per-granule header reads are scalar loads
   // (lgkmcnt) that never wait behind the prefetch loads or PCM stores (vmcnt)
@@ -1908,12 +1919,26 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     uint32_t base = 0;
     if (lane_fresh() == 0) base = atomicAdd(zone_count, n_pieces);
     base = __builtin_amdgcn_readfirstlane(base);  // lane 0 is the first active lane
-    for (uint32_t i = 0; i < nz; i++) {
-      const uint32_t zs = __builtin_amdgcn_readfirstlane(s.zone[i][0]), ze = __builtin_amdgcn_readfirstlane(s.zone[i][1]);
-      const uint32_t np = (ze - zs + kZonePiece - 1) / kZonePiece;
-      const uint32_t l = (uint32_t)lane_fresh();
-      // (always below the capacity: zone_list_capacity counts every piece)
-      if (l < np && base + l < zone_cap) {
+    // Piece p of the chunk (its zones' pieces counted through) by lane
+    // p % kLanes, in as many rounds as it takes: a zone of more than kLanes
+    // pieces (over 1,024 granules) used to lose the pieces past the lanes.
+    // Each lane finds its piece's zone itself.  (One flat loop, not a strided
+    // loop per zone: this form leaves the granule loop's instructions as they
+    // were, the other cost it 18 scalar copies per granule)
+    // The guard holds for a list sized by zone_list_capacity, which counts
+    // every piece; a shorter one (launch_fast checks only kZoneListPerChunk
+    // per chunk) drops pieces.
+    for (uint32_t p = (uint32_t)lane_fresh(); p < n_pieces; p += kLanes) {
+      if (base + p >= zone_cap) break;
+      uint32_t zs = 0, ze = 0, l = p;  // the zone of piece p, and p's index in it
+      for (uint32_t i = 0; i < nz; i++) {
+        zs = s.zone[i][0];
+        ze = s.zone[i][1];
+        const uint32_t np = (ze - zs + kZonePiece - 1) / kZonePiece;
+        if (l < np) break;
+        l -= np;
+      }
+      {
         const uint32_t ps = zs + l * kZonePiece, pe = min(ps + kZonePiece, ze);
         ChunkDesc z;
         z.out_first = ps;
@@ -1928,9 +1953,8 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
         // launch runs in this launch's format, and the other formats do not
         // read the field: their code stays as it was)
         z.stream_n = kFmt == (int)MP3G_OUT_F32_PLANAR ? cd.stream_n : 0u;
-        zone_list[base + l] = z;
+        zone_list[base + p] = z;
       }
-      base += np;
     }
   }
   // (counting build) a chunk counts its flagged granules even when none of

@@ -69,9 +69,12 @@ constexpr int kVariantExact4 = 4;
 // hybrid output -- to the list as chunks of their own, counting them; a
 // second launch (the exact v4 kernel over the list) decodes them in the
 // reference's order and, when its last workgroup is done, empties the list
-// for the next launch.  zone_list_capacity entries (the pieces of the
-// kZoneListPerChunk zones a chunk records at most) never overflow it, and
-// launch_fast refuses a list of fewer than kZoneListPerChunk per chunk (the
+// for the next launch.  A list of zone_list_capacity entries holds every
+// piece of the kZoneListPerChunk zones a chunk records at most, however long
+// the zones are (tests/test_zone_model_cpu.py restates the bound); the fast
+// kernel drops the pieces past the capacity it is given.  launch_fast itself
+// only refuses a list of fewer than kZoneListPerChunk entries per chunk, which
+// is less than that: both callers size theirs with zone_list_capacity (the
 // production kernel has no in-wave fallback).  Device memory of the plan (or pipeline) that
 // owns it, laid out as
 //   uint32 [0] zones listed, [1] zone-launch workgroups done, [2] capacity,
@@ -102,8 +105,11 @@ struct ZoneScratch {
 inline size_t zone_scratch_bytes(uint32_t cap) { return 32 + (size_t)cap * sizeof(ChunkDesc); }
 // Zero header + capacity (synchronous; once per allocation).
 hipError_t zone_scratch_init(void* p, uint32_t cap);
-// zones: the fast kernel's deferred hot zones (required in fast mode, with
-// room for kZoneListPerChunk per chunk: hipErrorInvalidValue otherwise); hot_stats: run the counting build, which adds
+// zones: the fast kernel's deferred hot zones (required in fast mode; a list
+// of fewer than kZoneListPerChunk entries per chunk is hipErrorInvalidValue,
+// but only one of zone_list_capacity entries is sure to hold every piece: a
+// shorter one passes this check and loses the pieces past its end, whose
+// granules then keep the fast transforms' output); hot_stats: run the counting build, which adds
 // its hot-granule work to the scratch's counters (the other kernels ignore both).
 // out_format: MP3G_OUT_* -- d_out holds int16 or float32 samples accordingly;
 // the one-wave kernels (fast v3, exact v4) have an instantiation per format,
