@@ -168,6 +168,15 @@ def lib():
             L.mp3g_fbank_execute.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
             L.mp3g_fbank_logf.argtypes = [vp, u64, vp]
             L.mp3g_fbank_logf.restype = None
+        if hasattr(L, "mp3g_stft_create"):
+            L.mp3g_stft_create.argtypes = [C.c_int] * 7 + [C.c_double] * 2 + [C.c_int, C.c_float, u32, C.POINTER(vp)]
+            L.mp3g_stft_free.argtypes = [vp]
+            L.mp3g_stft_free.restype = None
+            L.mp3g_stft_info.argtypes = [vp, C.POINTER(u32)] + [C.POINTER(vp)] * 4 + [C.POINTER(u32)]
+            L.mp3g_stft_frames.argtypes = [vp, u64]
+            L.mp3g_stft_frames.restype = u64
+            L.mp3g_stft_host.argtypes = [vp, vp, u64, u64, vp, u64]
+            L.mp3g_stft_execute.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
         L.mp3g_lame_parse.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo)]
         L.mp3g_lame_parse_reader.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo), C.POINTER(C.c_size_t)]
         L.mp3g_lame_total_delay.argtypes = [C.POINTER(_LameInfo)]
@@ -1092,6 +1101,149 @@ def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_leng
     finally:
         fb.close()
     return feats, flen, end_status, rates
+
+
+# ---- STFT and mel spectrograms of decoded rows (include/mp3g.h) ----------------
+STFT_CENTER = 1
+STFT_MEL_HTK = 2
+STFT_MEL_NORM = 4
+STFT_OUTPUTS = {"complex": 0, "power": 1, "magnitude": 2}
+STFT_LOGS = {None: 0, "ln": 1, "log10": 2}
+
+
+class STFT:
+    """STFT and mel spectrograms of float32 rows (mp3g_stft_*): a Hann-windowed
+    STFT by FFT for n_fft in {256, .., 4096}, stored as "complex" bins, "power"
+    or "magnitude", optionally through a mel filter bank (n_mels > 0; Slaney's
+    scale or htk, norm = Slaney's area normalisation) and a logarithm (log =
+    "ln" or "log10" of max(value, floor)).  The transform is one fixed network
+    of float32 butterflies that host and device both compile, so the device call
+    (execute) equals the host reference (host) bit for bit.  device=None (or -1)
+    makes a host-only object; fmax=0 means rate / 2; win_length=None means
+    n_fft."""
+
+    def __init__(self, rate, n_fft=2048, hop=512, win_length=None, output="power", n_mels=0, fmin=0.0, fmax=0.0,
+                 htk=False, norm=True, log=None, floor=None, center=True, device=None):
+        self._h = C.c_void_p()
+        if output not in STFT_OUTPUTS or log not in STFT_LOGS:
+            raise Mp3gError(1, "STFT: output is complex, power or magnitude; log is None, ln or log10")
+        self.device = -1 if device is None else int(device)
+        self.rate, self.n_fft, self.hop, self.n_mels = int(rate), int(n_fft), int(hop), int(n_mels)
+        self.win_length = self.n_fft if win_length is None else int(win_length)
+        self.output, self.log, self.floor = output, log, floor
+        self.center, self.htk, self.norm = bool(center), bool(htk), bool(norm)
+        self.flags = (STFT_CENTER if center else 0) | (STFT_MEL_HTK if htk else 0) | (STFT_MEL_NORM if norm else 0)
+        _check(lib().mp3g_stft_create(self.device, self.rate, self.n_fft, self.win_length, self.hop,
+                                      STFT_OUTPUTS[output], self.n_mels, float(fmin), float(fmax), STFT_LOGS[log],
+                                      0.0 if floor is None else float(floor), self.flags, C.byref(self._h)))
+        k, t = C.c_uint32(), C.c_uint32()
+        p = [C.c_void_p() for _ in range(4)]
+        _check(lib().mp3g_stft_info(self._h, C.byref(k), *[C.byref(q) for q in p], C.byref(t)))
+        self.K, self.tile_frames = k.value, t.value
+        self.pad = self.n_fft // 2 if center else 0
+        self.complex = output == "complex"
+        self.bins = self.n_mels or self.K
+
+        def view(q, ctype, shape):  # a view of the library's table: valid while this object lives
+            return np.ctypeslib.as_array(C.cast(q, C.POINTER(ctype)), shape=shape)
+        self.window = view(p[0], C.c_float, (self.n_fft,))
+        self.twiddles = view(p[1], C.c_float, (self.n_fft, 2))
+        self.wm = view(p[2], C.c_float, (self.n_mels, self.K)) if self.n_mels else None
+        self.support = view(p[3], C.c_uint32, (self.n_mels, 2)) if self.n_mels else None
+
+    def frames(self, T):
+        """The frames a row of T samples has (mp3g_stft_frames)."""
+        return int(lib().mp3g_stft_frames(self._h, int(T)))
+
+    def host(self, x, n_frames=None, frame_stride=None):
+        """The reference on the CPU (mp3g_stft_host): [bins, n_frames] float32 of
+        the float32 row x (n_frames: all by default), complex64 for "complex";
+        with a frame_stride the full [bins, frame_stride] buffer, zeros where
+        nothing is written."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = self.frames(len(x)) if n_frames is None else int(n_frames)
+        stride = n if frame_stride is None else int(frame_stride)
+        out = np.zeros((self.bins, max(stride, 0)) + ((2,) if self.complex else ()), np.float32)
+        _check(lib().mp3g_stft_host(self._h, _ptr(x) if len(x) else None, len(x), n, _ptr(out) if out.size else None,
+                                    stride))
+        return out.view(np.complex64)[..., 0] if self.complex else out
+
+    def execute(self, d_src, d_out=None, n_frames=None, stream=None):
+        """The device call (mp3g_stft_execute): d_src float32 [B, C, T] (C = 1 or
+        2) or [B, T], contiguous on this object's device; d_out float32 [B, (C,)
+        bins, S] -- "complex": [B, (C,) K, S, 2] -- with S >= n_frames (made
+        here when None: S = n_frames, all frames by default).  Writes n_frames
+        entries of each bin row, nothing else.  One launch, asynchronous on
+        `stream` (a hipStream_t; None = the current torch stream).  Returns
+        d_out, for "complex" as a complex64 view [B, (C,) K, S]."""
+        import torch
+        if d_src.dtype != torch.float32 or not d_src.is_contiguous() or d_src.dim() not in (2, 3) or not d_src.is_cuda:
+            raise ValueError("STFT.execute: a contiguous float32 device tensor [B, C, T] or [B, T]")
+        B, T = int(d_src.shape[0]), int(d_src.shape[-1])
+        planes = int(d_src.shape[1]) if d_src.dim() == 3 else 1
+        n = self.frames(T) if n_frames is None else int(n_frames)
+        lead = (B, planes) if d_src.dim() == 3 else (B,)
+        tail = (2,) if self.complex else ()
+        if d_out is None:
+            d_out = torch.empty(lead + (self.bins, n) + tail, dtype=torch.float32, device=d_src.device)
+        if d_out.is_complex():
+            d_out = torch.view_as_real(d_out)
+        S = int(d_out.shape[len(lead) + 1]) if d_out.dim() == len(lead) + 2 + len(tail) else -1
+        if (d_out.dtype != torch.float32 or not d_out.is_contiguous() or not d_out.is_cuda
+                or tuple(d_out.shape) != lead + (self.bins, S) + tail):
+            raise ValueError("STFT.execute: d_out is a contiguous float32 device tensor [B, (C,) bins, S(, 2)]")
+        if stream is None:
+            stream = torch.cuda.current_stream(d_src.device).cuda_stream
+        _check(lib().mp3g_stft_execute(self._h, C.c_void_p(d_src.data_ptr()) if d_src.numel() else None, B, planes, T,
+                                       C.c_void_p(d_out.data_ptr()) if d_out.numel() else None, n, S,
+                                       C.c_void_p(stream) if stream else None))
+        return torch.view_as_complex(d_out) if self.complex else d_out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.window = self.twiddles = self.wm = self.support = None
+            lib().mp3g_stft_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def decode_windows_stft_tensor(datas, starts, n_samples, rate, n_fft=2048, hop=512, win_length=None, output="power",
+                               n_mels=0, fmin=0.0, fmax=0.0, htk=False, norm=True, log=None, floor=None, center=True,
+                               n_frames=None, mode=MODE_EXACT, out_format=OUT_F32_MONO, gapless=False, quality="fast",
+                               n_threads=0, device=0):
+    """decode_windows_resampled_tensor followed by one STFT.execute on the same
+    torch stream: the spectrogram (or mel spectrogram) of each stream's window
+    [starts[k], starts[k] + n_samples) at `rate`, zero padding included.  F =
+    n_frames, by default n_samples // hop with center (which drops the last
+    frame, as decode_windows_logmel_tensor does) and every frame without.
+
+    Returns (features, frame_lengths, end_status, rates): features [B, bins, F]
+    (OUT_F32_MONO) or [B, 2, bins, F] (OUT_F32_PLANAR) on cuda:device, float32
+    or, for output="complex", complex64; equal to STFT.host on the rows of
+    decode_windows_resampled_tensor bit for bit; frame_lengths int64[B] = min(F,
+    ceil(lengths / hop)), the frames that start inside each stream's valid
+    samples."""
+    import torch
+    st = STFT(rate, n_fft, hop, win_length, output, n_mels, fmin, fmax, htk, norm, log, floor, center, device=device)
+    try:
+        T = int(n_samples)
+        avail = st.frames(T)
+        F = (min(avail, T // st.hop) if center else avail) if n_frames is None else int(n_frames)
+        if F < 0 or F > avail:
+            raise Mp3gError(1, "more frames than a row of n_samples has")
+        batch, lengths, end_status, rates = decode_windows_resampled_tensor(
+            datas, starts, T, rate, mode=mode, out_format=out_format, gapless=gapless, quality=quality,
+            n_threads=n_threads, device=device)
+        feats = st.execute(batch, n_frames=F)
+        torch.cuda.current_stream(feats.device).synchronize()
+    finally:
+        st.close()
+    return feats, np.minimum(F, -(-lengths // st.hop)), end_status, rates
 
 
 def _host_buffer(out, want_int16, want_float32=False):

@@ -54,7 +54,8 @@ extern "C" {
  *    mp3g_plan_execute_windows; sample-rate conversion of decoded rows --
  *    mp3g_resampler_*, mp3g_resample_host, mp3g_resample_rows and
  *    mp3g_stream_rates; log-mel features of decoded rows -- mp3g_logmel_*;
- *    Kaldi filter-bank features of decoded rows -- mp3g_fbank_*.) */
+ *    Kaldi filter-bank features of decoded rows -- mp3g_fbank_*; STFT and mel
+ *    spectrograms of decoded rows -- mp3g_stft_*.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -799,6 +800,111 @@ int mp3g_fbank_execute(const mp3g_fbank* fb, const float* d_src, uint32_t n_rows
                        float* d_out, uint32_t n_frames, uint32_t mel_stride, void* hip_stream);
 /* Test hook: y[i] = mp3g_logf(x[i]) (normal positive finite x). */
 void mp3g_fbank_logf(const float* x, uint64_t n, float* y);
+
+/* ---- STFT and mel spectrograms of decoded rows --------------------------------
+ * The front ends of music and general audio at its native rate: an STFT by FFT
+ * for n_fft = P in {256, 512, 1024, 2048, 4096}, stored as complex bins, power
+ * or magnitude, with an optional mel filter bank (Slaney's or HTK's scale, with
+ * or without area normalisation) and an optional logarithm.  Every value is a
+ * fixed sequence of float32 operations, so the device call equals
+ * mp3g_stft_host bit for bit.  No reference counterpart.
+ *
+ * Parameters.  rate > 0; 1 <= win_length <= P; 1 <= hop <= P; output one of
+ * MP3G_STFT_COMPLEX / _POWER / _MAGNITUDE; n_mels in 0..128 (0: no mel bank,
+ * the K = P / 2 + 1 bins are the output); fmin, fmax as mp3g_logmel_create takes
+ * them; log one of MP3G_STFT_LOG_NONE / _LN / _LOG10; floor a normal positive
+ * float32 when log != NONE (ignored otherwise); flags MP3G_STFT_CENTER,
+ * MP3G_STFT_MEL_HTK, MP3G_STFT_MEL_NORM.  MP3G_STFT_COMPLEX with n_mels > 0 or a
+ * logarithm is MP3G_ERR_INVALID_ARGUMENT; an n_fft that is none of the five
+ * sizes or an n_mels outside 0..128 MP3G_ERR_UNSUPPORTED; every other bad value
+ * MP3G_ERR_INVALID_ARGUMENT; all before any device call, with *out = NULL.
+ *
+ * Framing is mp3g_logmel's: with MP3G_STFT_CENTER pad = P / 2, frame f reads
+ * xr[f hop - pad + n], n < P, xr the row reflected about both ends, T > pad,
+ * frames 0 .. T / hop; without it pad = 0 and the frames are 0 .. (T - P) / hop.
+ *
+ * Tables, computed in float64 and rounded once to float32:
+ *   w[n], n < P: the periodic Hann window of win_length centred in the frame
+ *     (torch.stft): L = (P - win_length) / 2, w[L + j] = 0.5 - 0.5 cos(2 pi j /
+ *     win_length) for j < win_length, 0 elsewhere; win_length = 1: w[L] = 1.
+ *   tw[k] = (cos(2 pi k / P), -sin(2 pi k / P)), k < P; k a multiple of P / 4 is
+ *     exactly (1, 0), (0, -1), (-1, 0), (0, 1).
+ *   Wm[m][k]: triangles in Hz between n_mels + 2 points equally spaced on the
+ *     mel scale (Slaney's as in mp3g_logmel; MP3G_STFT_MEL_HTK: 2595 log10(1 +
+ *     f / 700)), as librosa.filters.mel and torchaudio's melscale_fbanks build
+ *     them; MP3G_STFT_MEL_NORM scales filter m by 2 / (its width in Hz).
+ *
+ * Features, all float32; the order is part of the contract:
+ *   v[n] = w[n] * xr[f hop - pad + n]                     (one rounded product)
+ *   z[n] = v[2 n] + i v[2 n + 1], n < N = P / 2
+ *   Z = FFT_N(z): decimation in frequency, in place; radix-4 passes over blocks
+ *     of len = N, N / 4, .. >= 4, then a radix-2 pass if len = 2 is left.  The
+ *     radix-4 butterfly at block base b, n < q = len / 4, x_r = z[b + n + r q]:
+ *       t0 = x0 + x2, t1 = x0 - x2, t2 = x1 + x3, t3 = -i (x1 - x3)
+ *       z[b+n] = t0 + t2,            z[b+n+q]  = (t1 + t3) tw[n P / len],
+ *       z[b+n+2q] = (t0 - t2) tw[2 n P / len], z[b+n+3q] = (t1 - t3) tw[3 n P / len]
+ *     (radix 2: x0 + x1, x0 - x1).  A product (a + i b)(c + i d), c + i d the
+ *     table entry, is t = b * d, re = fmaf(a, c, -t), u = b * c, im = fmaf(a, d,
+ *     u); with a table index that is a multiple of P / 4 it is a move with
+ *     negations.  Z[k] stands where k's digits (base 4 from the low end, then
+ *     the last bit) are reversed.
+ *   E = (Z[k].re + Z[N-k].re, Z[k].im - Z[N-k].im), O = (Z[k].re - Z[N-k].re,
+ *   Z[k].im + Z[N-k].im), T = O tw[k], for 0 < k <= N / 2:
+ *     X[k]   = ((E.re + T.im) * 0.5f, (E.im - T.re) * 0.5f)
+ *     X[N-k] = ((E.re - T.im) * 0.5f, (-E.im - T.re) * 0.5f)
+ *   (bin N / 2 is X[k]'s formula at k = N / 2: the two differ in a zero's sign)
+ *   X[0] = (Z[0].re + Z[0].im, +0), X[N] = (Z[0].re - Z[0].im, +0)
+ *   -- torch.stft's sign; a frame's bits depend on its own P samples only.
+ *   MP3G_STFT_COMPLEX stores (re, im); _POWER p = fmaf(re, re, im * im);
+ *   _MAGNITUDE sqrtf(p), correctly rounded.
+ *   n_mels > 0: mel = +0; for k = lo_m .. hi_m: mel = fmaf(Wm[m][k], s[k], mel),
+ *     s the power or the magnitude (empty filters allowed).
+ *   log: y = mp3g_logf(max(s, floor)) or mp3g_log10f(max(s, floor)), the
+ *     logarithms of the two feature objects above.  No clamp.
+ *
+ * Domain: finite samples with |x| <= 2^20; float32 subnormals are kept.
+ * Output, frequency-major: float [row][plane][bins][frame_stride] with bins =
+ * n_mels ? n_mels : K; MP3G_STFT_COMPLEX: float [row][plane][K][frame_stride][2]
+ * (torch.view_as_real of torch.stft's [.., K, F]).  n_frames entries are
+ * written per bin row, nothing else. */
+#define MP3G_STFT_CENTER 1u
+#define MP3G_STFT_MEL_HTK 2u
+#define MP3G_STFT_MEL_NORM 4u
+#define MP3G_STFT_COMPLEX 0
+#define MP3G_STFT_POWER 1
+#define MP3G_STFT_MAGNITUDE 2
+#define MP3G_STFT_LOG_NONE 0
+#define MP3G_STFT_LOG_LN 1
+#define MP3G_STFT_LOG_LOG10 2
+#define MP3G_STFT_MIN_FFT 256
+#define MP3G_STFT_MAX_FFT 4096
+#define MP3G_STFT_MAX_MELS 128
+typedef struct mp3g_stft mp3g_stft;
+/* Builds the tables; device >= 0 also uploads them to that device (once),
+ * device = -1 makes a host-only object. */
+int mp3g_stft_create(int device, int rate, int n_fft, int win_length, int hop, int output, int n_mels, double fmin,
+                     double fmax, int log, float floor, uint32_t flags, mp3g_stft** out);
+void mp3g_stft_free(mp3g_stft* st);
+/* K, the window float [n_fft], the twiddles float [n_fft][2], Wm float
+ * [n_mels][K] and the supports uint32 [n_mels][2] = lo_m, hi_m (lo > hi: an
+ * empty filter; both NULL without a mel bank) -- all owned by the object -- and
+ * the frames a workgroup of the device call produces (any may be NULL). */
+int mp3g_stft_info(const mp3g_stft* st, uint32_t* K, const float** window, const float** twiddles, const float** wm,
+                   const uint32_t** support, uint32_t* tile_frames);
+/* The frames a row of T samples has (0: none, or T >= 2^62). */
+uint64_t mp3g_stft_frames(const mp3g_stft* st, uint64_t T);
+/* The definition above in plain C++ (the reference the device call equals):
+ * out[b * frame_stride + f] (MP3G_STFT_COMPLEX: out[(b * frame_stride + f) * 2
+ * + 0 / 1]) for b < bins, f < n_frames <= mp3g_stft_frames. */
+int mp3g_stft_host(const mp3g_stft* st, const float* x, uint64_t T, uint64_t n_frames, float* out,
+                   uint64_t frame_stride);
+/* d_src: float [n_rows][n_planes][T]; d_out as above.  Both are device pointers
+ * and the launch shape depends on none of their contents: one launch,
+ * asynchronous on hip_stream and graph-capturable; launches of one object need
+ * no ordering between them.  T < 2^31; n_frames <= mp3g_stft_frames(st, T),
+ * frame_stride >= n_frames. */
+int mp3g_stft_execute(const mp3g_stft* st, const float* d_src, uint32_t n_rows, uint32_t n_planes, uint32_t T,
+                      float* d_out, uint32_t n_frames, uint32_t frame_stride, void* hip_stream);
 
 /* ---- decoder: mp3.NewDecoder / io.Reader / io.Seeker (decode.go:27-388) ----
  * Scans on the host with read-ahead (headers, side info, reservoir) and
