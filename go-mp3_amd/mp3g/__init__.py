@@ -177,6 +177,18 @@ def lib():
             L.mp3g_stft_frames.restype = u64
             L.mp3g_stft_host.argtypes = [vp, vp, u64, u64, vp, u64]
             L.mp3g_stft_execute.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
+        if hasattr(L, "mp3g_mfcc_create"):
+            L.mp3g_mfcc_create.argtypes = [C.c_int] * 6 + [C.c_double] * 6 + [C.c_int, u32, C.POINTER(vp)]
+            L.mp3g_mfcc_free.argtypes = [vp]
+            L.mp3g_mfcc_free.restype = None
+            L.mp3g_mfcc_info.argtypes = [vp, C.POINTER(vp), C.POINTER(u32), C.POINTER(vp), C.POINTER(vp),
+                                         C.POINTER(C.c_float), C.POINTER(u32)]
+            L.mp3g_mfcc_frames.argtypes = [vp, u64]
+            L.mp3g_mfcc_frames.restype = u64
+            L.mp3g_mfcc_host.argtypes = [vp, vp, u64, u64, vp, u64]
+            L.mp3g_mfcc_execute.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
+            L.mp3g_cmvn_rows.argtypes = [C.c_int, vp, u32, u32, u32, u32, u32, vp, u32, vp]
+            L.mp3g_cmvn_host.argtypes = [vp, u32, u32, u32, u32, u32, vp, u32]
         L.mp3g_lame_parse.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo)]
         L.mp3g_lame_parse_reader.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo), C.POINTER(C.c_size_t)]
         L.mp3g_lame_total_delay.argtypes = [C.POINTER(_LameInfo)]
@@ -1100,6 +1112,221 @@ def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_leng
             flen = np.minimum(F, (lengths + fb.hop // 2) // fb.hop)
     finally:
         fb.close()
+    return feats, flen, end_status, rates
+
+
+# ---- Kaldi MFCC features of decoded rows, per-row normalisation (include/mp3g.h) --
+MFCC_USE_ENERGY = 4
+MFCC_RAW_ENERGY = 8
+CMVN_NORM_VARS = 1
+CMVN_MODES = {None: None, "mean": False, "mean_var": True}
+
+
+class MFCC:
+    """Kaldi's MFCC features of float32 rows (mp3g_mfcc_*; what
+    compute-mfcc-feats and torchaudio.compliance.kaldi.mfcc compute, without
+    dither, VTLN and htk_compat): FBank's log mel energies through Kaldi's DCT
+    matrix cut to n_ceps rows and the cepstral lifter, time-major; with
+    use_energy coefficient 0 is the frame's log energy -- raw_energy: after DC
+    removal, before pre-emphasis and window; else after the window -- floored at
+    log(energy_floor) when that is positive.  Every sum is ONE float32 FMA chain
+    in ascending order, so the device call (execute) equals the host reference
+    (host) bit for bit.  The object owns an FBank-equivalent front end whose
+    tables are the views cw, sw, wm, support and w; dct [n_ceps, n_mels] and
+    lifter [n_ceps] are its own.  device=None (or -1) makes a host-only
+    object."""
+
+    def __init__(self, rate=16000, frame_length_ms=25.0, frame_shift_ms=10.0, n_mels=23, n_ceps=13,
+                 cepstral_lifter=22.0, use_energy=True, raw_energy=True, energy_floor=0.0, low_freq=20.0,
+                 high_freq=0.0, preemphasis=0.97, remove_dc=True, window="povey", snip_edges=True, scale=32768.0,
+                 device=None):
+        self._h = C.c_void_p()
+        if window not in FBANK_WINDOWS:
+            raise Mp3gError(1, "MFCC: window is one of " + ", ".join(FBANK_WINDOWS))
+        self.device = -1 if device is None else int(device)
+        self.rate, self.n_mels, self.n_ceps = int(rate), int(n_mels), int(n_ceps)
+        # Kaldi's conversion of the durations to samples
+        self.N, self.hop = int(self.rate * 0.001 * frame_length_ms), int(self.rate * 0.001 * frame_shift_ms)
+        self.preemphasis, self.scale, self.window = float(preemphasis), float(scale), window
+        self.cepstral_lifter, self.energy_floor = float(cepstral_lifter), float(energy_floor)
+        self.remove_dc, self.snip_edges = bool(remove_dc), bool(snip_edges)
+        self.use_energy, self.raw_energy = bool(use_energy), bool(raw_energy)
+        self.flags = ((FBANK_REMOVE_DC if remove_dc else 0) | (FBANK_SNIP_EDGES if snip_edges else 0)
+                      | (MFCC_USE_ENERGY if use_energy else 0) | (MFCC_RAW_ENERGY if raw_energy else 0))
+        _check(lib().mp3g_mfcc_create(self.device, self.rate, self.N, self.hop, self.n_mels, self.n_ceps,
+                                      float(low_freq), float(high_freq), self.preemphasis, self.scale,
+                                      self.cepstral_lifter, self.energy_floor, FBANK_WINDOWS[window], self.flags,
+                                      C.byref(self._h)))
+        fb, nc, lef, in_lds = C.c_void_p(), C.c_uint32(), C.c_float(), C.c_uint32()
+        d, lf = C.c_void_p(), C.c_void_p()
+        _check(lib().mp3g_mfcc_info(self._h, C.byref(fb), C.byref(nc), C.byref(d), C.byref(lf), C.byref(lef),
+                                    C.byref(in_lds)))
+        pp, k, t = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        p = [C.c_void_p() for _ in range(5)]
+        _check(lib().mp3g_fbank_info(fb, C.byref(pp), C.byref(k), *[C.byref(q) for q in p], C.byref(t)))
+        self.P, self.K, self.tile_frames = pp.value, k.value, t.value
+        self.log_energy_floor, self.dct_in_lds = float(lef.value), bool(in_lds.value)
+
+        def view(q, ctype, shape):  # a view of the library's table: valid while this object lives
+            return np.ctypeslib.as_array(C.cast(q, C.POINTER(ctype)), shape=shape)
+        self.dct = view(d, C.c_float, (self.n_ceps, self.n_mels))
+        self.lifter = view(lf, C.c_float, (self.n_ceps,))
+        self.cw = view(p[0], C.c_float, (self.K, self.N))
+        self.sw = view(p[1], C.c_float, (self.K, self.N))
+        self.wm = view(p[2], C.c_float, (self.n_mels, self.K))
+        self.support = view(p[3], C.c_uint32, (self.n_mels, 2))
+        self.w = view(p[4], C.c_float, (self.N,))
+
+    def frames(self, T):
+        """The frames a row of T samples has (mp3g_mfcc_frames)."""
+        return int(lib().mp3g_mfcc_frames(self._h, int(T)))
+
+    def host(self, x, n_frames=None, cep_stride=None):
+        """The reference on the CPU (mp3g_mfcc_host): features [n_frames,
+        n_ceps] of the float32 row x (n_frames: all by default); with a
+        cep_stride the full [n_frames, cep_stride] buffer, zeros where nothing
+        is written."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = self.frames(len(x)) if n_frames is None else int(n_frames)
+        stride = self.n_ceps if cep_stride is None else int(cep_stride)
+        out = np.zeros((max(n, 0), max(stride, 0)), np.float32)
+        _check(lib().mp3g_mfcc_host(self._h, _ptr(x) if len(x) else None, len(x), n, _ptr(out) if out.size else None,
+                                    stride))
+        return out
+
+    def execute(self, d_src, d_out=None, stream=None):
+        """The device call (mp3g_mfcc_execute): d_src float32 [B, C, T] (C = 1
+        or 2) or [B, T], contiguous on this object's device; d_out float32
+        [B, C, F, S] or [B, F, S] with F <= frames(T) and S >= n_ceps (made here
+        when None: every frame, S = n_ceps).  Writes the n_ceps features of each
+        of the F frames, nothing else.  One launch, asynchronous on `stream` (a
+        hipStream_t; None = the current torch stream).  Returns d_out."""
+        import torch
+        if d_src.dtype != torch.float32 or not d_src.is_contiguous() or d_src.dim() not in (2, 3) or not d_src.is_cuda:
+            raise ValueError("MFCC.execute: a contiguous float32 device tensor [B, C, T] or [B, T]")
+        B, T = int(d_src.shape[0]), int(d_src.shape[-1])
+        planes = int(d_src.shape[1]) if d_src.dim() == 3 else 1
+        lead = (B, planes) if d_src.dim() == 3 else (B,)
+        if d_out is None:
+            d_out = torch.empty(lead + (self.frames(T), self.n_ceps), dtype=torch.float32, device=d_src.device)
+        if (d_out.dtype != torch.float32 or not d_out.is_contiguous() or not d_out.is_cuda
+                or d_out.dim() != len(lead) + 2 or tuple(d_out.shape[:-2]) != lead):
+            raise ValueError("MFCC.execute: d_out is a contiguous float32 device tensor [B, (C,) F, S]")
+        if stream is None:
+            stream = torch.cuda.current_stream(d_src.device).cuda_stream
+        _check(lib().mp3g_mfcc_execute(self._h, C.c_void_p(d_src.data_ptr()) if d_src.numel() else None, B, planes, T,
+                                       C.c_void_p(d_out.data_ptr()) if d_out.numel() else None,
+                                       int(d_out.shape[-2]), int(d_out.shape[-1]), C.c_void_p(stream) if stream else None))
+        return d_out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.dct = self.lifter = self.cw = self.sw = self.wm = self.support = self.w = None
+            lib().mp3g_mfcc_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cmvn_host(feats, frame_lengths, norm_vars=False, n_cols=None):
+    """The reference on the CPU (mp3g_cmvn_host): a normalised copy of the
+    float32 array feats [B, F, S] or [B, C, F, S] -- per row and plane, over
+    the row's first min(frame_lengths[b], F) frames, every column below n_cols
+    (all S by default) minus its mean in double, with norm_vars divided by its
+    standard deviation (the variance floored at 1e-20).  Frames past the length
+    and columns from n_cols on are copied."""
+    out = np.array(feats, dtype=np.float32, order="C", copy=True)
+    if out.ndim not in (3, 4):
+        raise ValueError("cmvn_host: feats is [B, F, S] or [B, C, F, S]")
+    B, planes = out.shape[0], (out.shape[1] if out.ndim == 4 else 1)
+    lengths = np.ascontiguousarray(frame_lengths, dtype=np.uint32)
+    if lengths.shape != (B,):
+        raise ValueError("cmvn_host: one frame length per row")
+    cols = out.shape[-1] if n_cols is None else int(n_cols)
+    _check(lib().mp3g_cmvn_host(_ptr(out) if out.size else None, B, planes, out.shape[-2], out.shape[-1], cols,
+                                _ptr(lengths) if B else None, CMVN_NORM_VARS if norm_vars else 0))
+    return out
+
+
+def cmvn(feats, frame_lengths, norm_vars=False, stream=None, n_cols=None):
+    """The device call (mp3g_cmvn_rows): normalises the contiguous float32
+    device tensor feats [B, F, S] or [B, C, F, S] in place, as cmvn_host
+    states it and bit for bit.  frame_lengths: a device tensor or anything
+    array-like, one count per row (copied to the device as int32 when it is not
+    there; values above F mean F).  One launch, asynchronous on `stream` (a
+    hipStream_t; None = the current torch stream).  Returns feats."""
+    import torch
+    if (not torch.is_tensor(feats) or feats.dtype != torch.float32 or not feats.is_contiguous() or not feats.is_cuda
+            or feats.dim() not in (3, 4)):
+        raise ValueError("cmvn: a contiguous float32 device tensor [B, F, S] or [B, C, F, S]")
+    B, planes = int(feats.shape[0]), (int(feats.shape[1]) if feats.dim() == 4 else 1)
+    if torch.is_tensor(frame_lengths) and frame_lengths.is_cuda:
+        lengths = frame_lengths.to(torch.int32).contiguous()
+    else:
+        host = np.ascontiguousarray(np.minimum(np.asarray(frame_lengths, dtype=np.int64), 2 ** 31 - 1), dtype=np.int32)
+        lengths = torch.from_numpy(host).to(feats.device)
+    if tuple(lengths.shape) != (B,):
+        raise ValueError("cmvn: one frame length per row")
+    cols = int(feats.shape[-1]) if n_cols is None else int(n_cols)
+    if stream is None:
+        stream = torch.cuda.current_stream(feats.device).cuda_stream
+    _check(lib().mp3g_cmvn_rows(feats.device.index or 0, C.c_void_p(feats.data_ptr()) if feats.numel() else None, B,
+                                planes, int(feats.shape[-2]), int(feats.shape[-1]), cols,
+                                C.c_void_p(lengths.data_ptr()) if B else None, CMVN_NORM_VARS if norm_vars else 0,
+                                C.c_void_p(stream) if stream else None))
+    return feats
+
+
+_cmvn_rows = cmvn  # (decode_windows_mfcc_tensor has a parameter of that name)
+
+
+def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_length_ms=25.0, frame_shift_ms=10.0,
+                               n_mels=23, n_ceps=13, cepstral_lifter=22.0, use_energy=True, raw_energy=True,
+                               energy_floor=0.0, low_freq=20.0, high_freq=0.0, preemphasis=0.97, remove_dc=True,
+                               window="povey", snip_edges=True, scale=32768.0, cmvn=None, n_frames=None,
+                               mode=MODE_EXACT, out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0,
+                               device=0):
+    """decode_windows_resampled_tensor, MFCC.execute and, with cmvn = "mean"
+    or "mean_var", the per-row normalisation over each stream's own frames, all
+    on the current torch stream: Kaldi's MFCC features of each stream's window
+    [starts[k], starts[k] + n_samples) at `rate`, zero padding included.
+    F = n_frames, by default every frame a row of n_samples has.
+
+    Returns (features, frame_lengths, end_status, rates): features [B, F,
+    n_ceps] (OUT_F32_MONO) or [B, 2, F, n_ceps] (OUT_F32_PLANAR) on cuda:device,
+    equal to MFCC.host (then cmvn_host) on the rows of
+    decode_windows_resampled_tensor bit for bit; frame_lengths int64[B] as
+    decode_windows_fbank_tensor counts them.  Frames past a stream's
+    frame_lengths are not normalised."""
+    import torch
+    if cmvn not in CMVN_MODES:
+        raise Mp3gError(1, "decode_windows_mfcc_tensor: cmvn is None, 'mean' or 'mean_var'")
+    mf = MFCC(rate, frame_length_ms, frame_shift_ms, n_mels, n_ceps, cepstral_lifter, use_energy, raw_energy,
+              energy_floor, low_freq, high_freq, preemphasis, remove_dc, window, snip_edges, scale, device=device)
+    try:
+        T = int(n_samples)
+        avail = mf.frames(T)
+        F = avail if n_frames is None else int(n_frames)
+        if F < 0 or F > avail:
+            raise Mp3gError(1, "more frames than a row of n_samples has")
+        batch, lengths, end_status, rates = decode_windows_resampled_tensor(
+            datas, starts, T, rate, mode=mode, out_format=out_format, gapless=gapless, quality=quality,
+            n_threads=n_threads, device=device)
+        feats = torch.empty(tuple(batch.shape[:-1]) + (F, mf.n_ceps), dtype=torch.float32, device=batch.device)
+        mf.execute(batch, feats)
+        if snip_edges:
+            flen = np.clip((lengths - mf.N) // mf.hop + 1, 0, F)
+        else:
+            flen = np.minimum(F, (lengths + mf.hop // 2) // mf.hop)
+        if CMVN_MODES[cmvn] is not None:
+            _cmvn_rows(feats, flen, norm_vars=CMVN_MODES[cmvn])
+        torch.cuda.current_stream(feats.device).synchronize()
+    finally:
+        mf.close()
     return feats, flen, end_status, rates
 
 

@@ -55,7 +55,9 @@ extern "C" {
  *    mp3g_resampler_*, mp3g_resample_host, mp3g_resample_rows and
  *    mp3g_stream_rates; log-mel features of decoded rows -- mp3g_logmel_*;
  *    Kaldi filter-bank features of decoded rows -- mp3g_fbank_*; STFT and mel
- *    spectrograms of decoded rows -- mp3g_stft_*.) */
+ *    spectrograms of decoded rows -- mp3g_stft_*; Kaldi MFCC features of
+ *    decoded rows -- mp3g_mfcc_*; per-row mean and variance normalisation --
+ *    mp3g_cmvn_rows and mp3g_cmvn_host.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -725,7 +727,8 @@ void mp3g_logmel_log10f(const float* x, uint64_t n, float* y);
  * or n_mels outside the supported range MP3G_ERR_UNSUPPORTED; both before any
  * device call, with *out = NULL.
  * Not offered: dither (random, so not reproducible), the energy column, VTLN,
- * subtract_mean, and magnitude (non-power) or non-log output.
+ * subtract_mean, and magnitude (non-power) or non-log output (the energy is
+ * mp3g_mfcc's coefficient 0, subtract_mean is mp3g_cmvn_rows; both below).
  *
  * Framing.  One row is a float32 signal x[0, T) (a plane of the dense batch,
  * its zero padding included).  A row with T < N has no frames, in both modes.
@@ -800,6 +803,104 @@ int mp3g_fbank_execute(const mp3g_fbank* fb, const float* d_src, uint32_t n_rows
                        float* d_out, uint32_t n_frames, uint32_t mel_stride, void* hip_stream);
 /* Test hook: y[i] = mp3g_logf(x[i]) (normal positive finite x). */
 void mp3g_fbank_logf(const float* x, uint64_t n, float* y);
+
+/* ---- Kaldi MFCC features of decoded rows --------------------------------------
+ * Kaldi's compute-mfcc-feats (what torchaudio.compliance.kaldi.mfcc restates):
+ * the filter-bank features above through a DCT and a cepstral lifter, with the
+ * frame's log energy as coefficient 0 -- the input of the x-vector / ECAPA
+ * speaker recipes, of language-ID systems and of the GMM recipes.  An mp3g_mfcc
+ * owns an mp3g_fbank built by mp3g_fbank_create from its front-end parameters
+ * and adds to it.  Every feature is a fixed sequence of float32 operations, so
+ * the device call equals mp3g_mfcc_host bit for bit.  No reference counterpart.
+ *
+ * Parameters.  Everything mp3g_fbank_create takes, with the same checks and the
+ * same status codes; n_ceps in 1..n_mels; cepstral_lifter Q finite and >= 0 (0:
+ * no lifter); energy_floor 0 or a normal positive float32; flags
+ * MP3G_FBANK_REMOVE_DC, MP3G_FBANK_SNIP_EDGES, MP3G_MFCC_USE_ENERGY and
+ * MP3G_MFCC_RAW_ENERGY (without USE_ENERGY it is accepted and has no effect).  A
+ * violated relation, a non-finite value or an unknown flag is
+ * MP3G_ERR_INVALID_ARGUMENT, a range the front end does not support
+ * MP3G_ERR_UNSUPPORTED; both before any device call, with *out = NULL.
+ * Not offered: htk_compat (the energy stays coefficient 0), dither and VTLN.
+ *
+ * Tables, computed in float64 and rounded once to float32, M = n_mels:
+ *   D[i][m], i < n_ceps: Kaldi's ComputeDctMatrix -- D[0][m] = sqrt(1 / M),
+ *   D[i][m] = sqrt(2 / M) cos(pi / M (m + 0.5) i)
+ *   lift[i] = 1 + 0.5 Q sin(pi i / Q); exactly 1.0f when Q = 0
+ *   lef = mp3g_logf(energy_floor) when the floor is positive
+ *
+ * Features, all float32.  s, mean, d, e, re, im, p and mel are mp3g_fbank's and
+ *   L[f][m] = mp3g_logf(max(mel, 0x1p-23f))
+ * is, with the same front-end parameters, mp3g_fbank_host's output bit for bit.
+ * The log energy, only with MP3G_MFCC_USE_ENERGY:
+ *   v[n] = d[n]                      (MP3G_MFCC_RAW_ENERGY: before pre-emphasis
+ *                                     and window, after DC removal)
+ *   v[n] = w[n] * e[n]               (otherwise; one rounded product)
+ *   en = +0; en = fmaf(v[n], v[n], en), n ascending over 0 .. N-1
+ *   le = mp3g_logf(max(en, 0x1p-23f));  if energy_floor > 0 and le < lef: le = lef
+ * The cepstra:
+ *   c = +0; c = fmaf(D[i][m], L[f][m], c), m ascending over 0 .. M-1
+ *   y[f][i] = c * lift[i]            (one rounded product, also when Q = 0)
+ *   y[f][0] = le                     (MP3G_MFCC_USE_ENERGY: after the lifter,
+ *                                     in place of c0, as in Kaldi)
+ * -- each sum ONE FMA chain in ascending order; the order is part of the
+ * contract.  Framing, frame counts, reflection and the sample domain are
+ * mp3g_fbank's.
+ * Output: float [row][plane][n_frames][cep_stride], cep_stride >= n_ceps, time-
+ * major.  n_ceps values are written per frame, nothing else. */
+#define MP3G_MFCC_USE_ENERGY 4u
+#define MP3G_MFCC_RAW_ENERGY 8u
+typedef struct mp3g_mfcc mp3g_mfcc;
+/* Builds the tables and the owned mp3g_fbank; device >= 0 also uploads them to
+ * that device (once), device = -1 makes a host-only object. */
+int mp3g_mfcc_create(int device, int rate, int N, int hop, int n_mels, int n_ceps, double low_freq, double high_freq,
+                     double preemph, double scale, double cepstral_lifter, double energy_floor, int window,
+                     uint32_t flags, mp3g_mfcc** out);
+void mp3g_mfcc_free(mp3g_mfcc* mf);
+/* The owned front end (for mp3g_fbank_info; not to be freed), n_ceps, D float
+ * [n_ceps][n_mels] and lift float [n_ceps] -- owned by the object --, lef (0
+ * without a floor) and whether the device call keeps D in LDS (any may be
+ * NULL). */
+int mp3g_mfcc_info(const mp3g_mfcc* mf, const mp3g_fbank** fbank, uint32_t* n_ceps, const float** dct,
+                   const float** lifter, float* log_energy_floor, uint32_t* dct_in_lds);
+/* The frames a row of T samples has: mp3g_fbank_frames of the front end. */
+uint64_t mp3g_mfcc_frames(const mp3g_mfcc* mf, uint64_t T);
+/* The definition above in plain C++ (the reference the device call equals):
+ * out[f * cep_stride + i] for f < n_frames <= mp3g_mfcc_frames, i < n_ceps. */
+int mp3g_mfcc_host(const mp3g_mfcc* mf, const float* x, uint64_t T, uint64_t n_frames, float* out,
+                   uint64_t cep_stride);
+/* d_src: float [n_rows][n_planes][T]; d_out: float [n_rows][n_planes][n_frames]
+ * [cep_stride].  Both are device pointers and the launch shape depends on none
+ * of their contents: one launch, asynchronous on hip_stream and graph-
+ * capturable.  T < 2^31; n_frames <= mp3g_mfcc_frames(mf, T), cep_stride >=
+ * n_ceps. */
+int mp3g_mfcc_execute(const mp3g_mfcc* mf, const float* d_src, uint32_t n_rows, uint32_t n_planes, uint32_t T,
+                      float* d_out, uint32_t n_frames, uint32_t cep_stride, void* hip_stream);
+
+/* ---- Per-row mean and variance normalisation -----------------------------------
+ * Kaldi's per-utterance apply-cmvn (subtract_mean, with MP3G_CMVN_NORM_VARS also
+ * the variance) on a time-major feature tensor float [n_rows][n_planes]
+ * [n_frames][stride] -- the output of mp3g_fbank_execute or mp3g_mfcc_execute --
+ * in place.  The batch is zero-padded, so every row brings its own frame count.
+ * For each plane of row r, column c < n_cols and n = min(lengths[r], n_frames);
+ * n = 0 writes nothing; otherwise, in double:
+ *   sum = 0; sum += (double)x[f][c], f ascending over 0 .. n-1;  mean = sum / n
+ *   with NORM_VARS: sq = 0; sq += (double)x[f][c] * (double)x[f][c] (the product
+ *   of two converted floats is exact);  var = sq / n - mean * mean (the product
+ *   rounded first);  vf = max((float)var, 1e-20f);  scale = 1.0f / sqrtf(vf)
+ *   y[f][c] = (float)((double)x[f][c] - mean), with NORM_VARS times scale (one
+ *   rounded float32 product), for f < n
+ * Frames f >= n and columns >= n_cols are not touched.  The device call equals
+ * the host call bit for bit.  stride < n_cols, an unknown flag or a null pointer
+ * with work to do is MP3G_ERR_INVALID_ARGUMENT; no rows, planes, frames or
+ * columns is MP3G_OK with nothing done.  mp3g_cmvn_rows: d_feats and d_lengths
+ * (uint32 [n_rows]) are device pointers; one launch, asynchronous on hip_stream
+ * and graph-capturable. */
+#define MP3G_CMVN_NORM_VARS 1u
+int mp3g_cmvn_rows(int device, float* d_feats, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames,
+                   uint32_t stride, uint32_t n_cols, const uint32_t* d_lengths, uint32_t flags, void* hip_stream);
+int mp3g_cmvn_host(float* feats, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames, uint32_t stride,
+                   uint32_t n_cols, const uint32_t* lengths, uint32_t flags);
 
 /* ---- STFT and mel spectrograms of decoded rows --------------------------------
  * The front ends of music and general audio at its native rate: an STFT by FFT
