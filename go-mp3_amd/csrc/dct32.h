@@ -18,6 +18,13 @@
 // v_pk_* instructions.  Reassociated like the rest of the fast mode (+-1 LSB
 // of PCM; tests/test_dct32.py checks it against float64).
 //
+// The fast kernel runs the scaled form, dct2_32_scaled_to: X[m] / kScale[m],
+// every post-twiddle as one packed instruction (its factor, the larger of its
+// cosine and sine, goes into the synthesis window's taps, which multiply
+// every X anyway): ~110 instructions.  dct2_32 / dct2_32_to are the plain
+// transform (the standalone polyphase kernel, tests/test_dct32.py;
+// tests/test_dct_scaled.py checks the scaled one and the scale tables).
+//
 // Output order: X leaves as 16 pairs (kPairM[t][0], kPairM[t][1]); the fast
 // kernel stores pair t in ring columns kColX[t], kColY[t] (kPosOfM: X[m]'s column).
 #pragma once
@@ -86,6 +93,8 @@ MP3G_D32 void fft4(f2& z0, f2& z1, f2& z2, f2& z3) {
 }
 
 // DCT4_16 of d (pairs dp[j] = (d[2j], d[2j+1])) -> 8 output pairs
+// (kScaled: each pair without its post-twiddle's factor, see kScale)
+template <bool kScaled = false>
 MP3G_D32 void dct4_16(const f2 dp[8], f2 out[8]) {
   f2 v[8];
 #pragma unroll
@@ -101,24 +110,32 @@ MP3G_D32 void dct4_16(const f2 dp[8], f2 out[8]) {
   const f2 V[8] = {v[0] + o0,          v[2] + o1, add_mi(v[4], v[5]), add_mi(v[6], w7),
                    v[0] - o0,          v[2] - o1, sub_mi(v[4], v[5]), sub_mi(v[6], w7)};
 #pragma unroll
-  for (int k = 0; k < 8; k++) out[k] = pk::post_tw(V[k], kPost16[k][0], kPost16[k][1]);
+  for (int k = 0; k < 8; k++) {
+    if constexpr (!kScaled) out[k] = pk::post_tw(V[k], kPost16[k][0], kPost16[k][1]);
+    else out[k] = k == 0 ? V[k] : pk::post_tw_s(V[k], kPost16[k][0], kPost16[k][1]);  // k = 0: (vr, vi), sigma (1, -1)
+  }
 }
 
 // DCT4_8 of b (pairs bp[j] = (b[2j], b[2j+1])) -> 4 output pairs (X[2k], X[7-2k])
+template <bool kScaled = false>
 MP3G_D32 void dct4_8(const f2 bp[4], f2 out[4]) {
   f2 v[4];
 #pragma unroll
   for (int n = 0; n < 4; n++) v[n] = pk::pre_tw2<0, 1>(bp[n], bp[3 - n], kPre8[n][0], kPre8[n][1]);
   fft4(v[0], v[1], v[2], v[3]);
 #pragma unroll
-  for (int k = 0; k < 4; k++) out[k] = pk::post_tw(v[k], kPost8[k][0], kPost8[k][1]);
+  for (int k = 0; k < 4; k++) {
+    if constexpr (!kScaled) out[k] = pk::post_tw(v[k], kPost8[k][0], kPost8[k][1]);
+    else out[k] = k == 0 ? v[k] : pk::post_tw_s(v[k], kPost8[k][0], kPost8[k][1]);
+  }
 }
 
 // X[m] = sum_k S[k] cos(pi m (2k+1) / 64) for one slot.  sp[j] = (S[2j], S[2j+1]);
 // out(t, xp) receives pair t = (X[kPairM[t][0]], X[kPairM[t][1]]) as soon as it
 // is computed (the caller stores it: fewer values live at once).
-template <class Out>
-MP3G_D32 void dct2_32_to(const f2 sp[16], Out out) {
+// kScaled: X[m] / kScale[m] instead (dct2_32_scaled_to below).
+template <bool kScaled, class Out>
+MP3G_D32 void dct2_32_impl(const f2 sp[16], Out out) {
   // fold 32 -> even part e (DCT2_16) and odd part d (DCT4_16)
   f2 ep[8], dp[8];
 #pragma unroll
@@ -129,7 +146,7 @@ MP3G_D32 void dct2_32_to(const f2 sp[16], Out out) {
   }
   {
     f2 x4[8];
-    dct4_16(dp, x4);  // pairs 0..7: m = 4k+1, 31-4k
+    dct4_16<kScaled>(dp, x4);  // pairs 0..7: m = 4k+1, 31-4k
 #pragma unroll
     for (int t = 0; t < 8; t++) out(t, x4[t]);
   }
@@ -143,7 +160,7 @@ MP3G_D32 void dct2_32_to(const f2 sp[16], Out out) {
   }
   {
     f2 x8[4];
-    dct4_8(bp, x8);  // pairs 8..11: m = 8k+2, 30-8k
+    dct4_8<kScaled>(bp, x8);  // pairs 8..11: m = 8k+2, 30-8k
 #pragma unroll
     for (int t = 0; t < 4; t++) out(8 + t, x8[t]);
   }
@@ -167,9 +184,56 @@ MP3G_D32 void dct2_32_to(const f2 sp[16], Out out) {
   // DCT2_4(a'): fold -> u (DCT2_2: m = 0, 16), w (DCT4_2: m = 8, 24)
   const f2 u = a1p0 + swp(a1p1);  // (a'0 + a'3, a'1 + a'2)
   const f2 w = a1p0 - swp(a1p1);  // (a'0 - a'3, a'1 - a'2)
-  out(14, (blo(u) + mk(u.y, -u.y)) * mk(1.0f, kR2));
-  out(15, fma2(bhi(w), mk(kC3, -kC1), blo(w) * mk(kC1, kC3)));
+  if constexpr (!kScaled) {
+    out(14, (blo(u) + mk(u.y, -u.y)) * mk(1.0f, kR2));
+    out(15, fma2(bhi(w), mk(kC3, -kC1), blo(w) * mk(kC1, kC3)));
+  } else {
+    out(14, blo(u) + mk(u.y, -u.y));        // sigma (1, kR2)
+    out(15, pk::post_tw_s(w, kC1, kC3));    // the unscaled line is post_tw(w, kC1, kC3): sigma kC1
+  }
 }
+
+template <class Out>
+MP3G_D32 void dct2_32_to(const f2 sp[16], Out out) {
+  dct2_32_impl<false>(sp, out);
+}
+
+// The scaled transform: out(t, xp) receives (X[m0] / kScale[m0], X[m1] /
+// kScale[m1]), m0, m1 = kPairM[t][0], kPairM[t][1].  The factor of a
+// post-twiddle, c (vr + t vi, t vr - vi) with t = s / c (pk::post_tw_s), is
+// left to the reader of X, which multiplies every X[m] by a table entry
+// anyway: 12 post-twiddles and the two last pairs take one packed instruction
+// instead of two, the identity twiddles (1, 0) none -- they leave (vr, vi)
+// for (vr, -vi), a sigma of -1.  16 of the transform's ~126 packed
+// instructions go.  0.707 <= |kScale[m]| <= 1.
+template <class Out>
+MP3G_D32 void dct2_32_scaled_to(const f2 sp[16], Out out) {
+  dct2_32_impl<true>(sp, out);
+}
+
+// sigma of X[m] and its inverse, natural m order, from the twiddle tables:
+// dct2_32_scaled_to leaves X[m] * kInvScale[m].
+struct Scale32 {
+  float v[32];
+  constexpr float operator[](int m) const { return v[m]; }
+};
+constexpr Scale32 make_scale32(bool inverse) {
+  float pair[16][2] = {};
+  for (int k = 0; k < 8; k++) pair[k][0] = pair[k][1] = pk::post_scale(kPost16[k][0], kPost16[k][1]);
+  for (int k = 0; k < 4; k++) pair[8 + k][0] = pair[8 + k][1] = pk::post_scale(kPost8[k][0], kPost8[k][1]);
+  pair[0][1] = -pair[0][1];  // identity twiddles: (vr, vi) stands for (vr, -vi)
+  pair[8][1] = -pair[8][1];
+  pair[12][0] = pair[12][1] = pair[13][0] = pair[13][1] = 1.0f;  // DCT4_4, direct
+  pair[14][0] = 1.0f;
+  pair[14][1] = kR2;
+  pair[15][0] = pair[15][1] = pk::post_scale(kC1, kC3);
+  Scale32 r{};
+  for (int t = 0; t < 16; t++)
+    for (int h = 0; h < 2; h++) r.v[kPairM[t][h]] = inverse ? 1.0f / pair[t][h] : pair[t][h];
+  return r;
+}
+constexpr Scale32 kScale = make_scale32(false);
+constexpr Scale32 kInvScale = make_scale32(true);
 
 MP3G_D32 void dct2_32(const f2 sp[16], f2 xp[16]) {
   dct2_32_to(sp, [&](int t, f2 v) { xp[t] = v; });

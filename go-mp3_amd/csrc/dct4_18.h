@@ -8,7 +8,9 @@
 // Cooley-Tukey), post-twiddle -- with every constant an instruction literal:
 // no coefficient table, so none of the 81 broadcast LDS reads per granule the
 // direct form needs (the fast kernel is LDS-bound).  Reassociated like the
-// rest of the fast mode (+-1 LSB of PCM).
+// rest of the fast mode (+-1 LSB of PCM).  The fast kernel's loop runs
+// dct4_18_pk_scaled, whose post-twiddles leave their factors (kScale9) to the
+// IMDCT window entries that multiply each output next.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -93,7 +95,9 @@ __host__ __device__ __forceinline__ void dft3p(pk::f2& a, pk::f2& b, pk::f2& c) 
   b = pk::fma_mi<false>(kH, d, t);  // t + kH (-i) d
   c = pk::fma_mi<true>(kH, d, t);
 }
-__host__ __device__ __forceinline__ void dct4_18_pk(const float x[18], pk::f2 P[9]) {
+// kScaled: P[k] without its post-twiddle's factor (dct4_18_pk_scaled below)
+template <bool kScaled>
+__host__ __device__ __forceinline__ void dct4_18_pk_impl(const float x[18], pk::f2 P[9]) {
   pk::f2 z[9];
 #pragma unroll
   for (int n = 0; n < 9; n++) {
@@ -109,8 +113,37 @@ __host__ __device__ __forceinline__ void dct4_18_pk(const float x[18], pk::f2 P[
 #pragma unroll
   for (int k1 = 0; k1 < 3; k1++) dft3p(z[3 * k1], z[3 * k1 + 1], z[3 * k1 + 2]);
 #pragma unroll
-  for (int k = 0; k < 9; k++) P[k] = pk::post_tw(z[3 * (k % 3) + k / 3], kPost[k][0], kPost[k][1]);
+  for (int k = 0; k < 9; k++) {
+    const pk::f2 y = z[3 * (k % 3) + k / 3];
+    if constexpr (!kScaled) P[k] = pk::post_tw(y, kPost[k][0], kPost[k][1]);
+    else P[k] = k == 0 ? y : pk::post_tw_s(y, kPost[k][0], kPost[k][1]);  // k = 0: (yr, yi) for (yr, -yi)
+  }
 }
+__host__ __device__ __forceinline__ void dct4_18_pk(const float x[18], pk::f2 P[9]) { dct4_18_pk_impl<false>(x, P); }
+
+// The scaled transform: P[k] = (X[2k] / kScale9[k][0], X[17-2k] / kScale9[k][1]).
+// Each post-twiddle leaves its factor c or s (pk::post_tw_s: one packed
+// instruction instead of two, the identity twiddle none) to the reader: the
+// fast kernel's overlap() multiplies both values of a pair by window entries,
+// which take the factor when the table is filled (kScaleX by X index).  10
+// of the ~80 packed instructions go.  0.707 <= |kScale9| <= 1; only the
+// identity twiddle's second value has a negative one.
+__host__ __device__ __forceinline__ void dct4_18_pk_scaled(const float x[18], pk::f2 P[9]) {
+  dct4_18_pk_impl<true>(x, P);
+}
+struct Scale9 {
+  float v[9][2];
+  constexpr const float* operator[](int k) const { return v[k]; }
+};
+constexpr Scale9 make_scale9() {
+  Scale9 r{};
+  for (int k = 0; k < 9; k++) r.v[k][0] = r.v[k][1] = pk::post_scale(kPost[k][0], kPost[k][1]);
+  r.v[0][1] = -r.v[0][1];
+  return r;
+}
+constexpr Scale9 kScale9 = make_scale9();
+// the factor of X[n], n = 0..17
+constexpr float kScaleX(int n) { return (n & 1) ? kScale9.v[(17 - n) / 2][1] : kScale9.v[n / 2][0]; }
 
 // Short blocks (imdct.go:88-94): the 12-point IMDCT of each window as a
 // direct sum with literal coefficients (6 inputs; no table in LDS either).

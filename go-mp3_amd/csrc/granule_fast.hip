@@ -27,6 +27,16 @@
 //   window      lane = (ch, i): 16 taps (V->X signs and x32767 folded in)
 //               over operand pairs of the column-major ring, s16 (L, R) pairs
 //               through one v_permlane32_swap per slot pair, stored at once.
+// Constant factors ride on tables the values are multiplied by anyway
+// (shared_init builds them once per workgroup): both transforms run in their
+// scaled forms, each post-twiddle one packed instruction short of its factor
+// -- the ring holds X[m] / sigma[m] (dct32::kScale) and the window's taps in
+// sh.dwin carry sigma by lane and tap parity, the long IMDCT windows in
+// sh.winp carry dct4::kScale9 -- and the 1/sqrt2 of MS stereo over every line
+// goes into that granule's band gains.  The scale never leaves the wave: the
+// entry state is divided by sigma on import and the exported state multiplied
+// by it, so mp3g_state stays in the V domain, and the hot tests read S, ahead
+// of the matrixing.
 // Hot granules (hybrid output above the magnitude bound kHotS / kHotL1) are
 // not redone here: the wave records their zones (the granules whose PCM
 // depends on them) and appends them to the launch's zone list, and a second
@@ -432,6 +442,8 @@ __device__ __forceinline__ float requant_gain(uint32_t xw, float g) {
 
 // X of a V block: X[m] = V[m-16] (m >= 16), -V[48-m] (m < 16).
 __device__ __forceinline__ float x_from_v(const float* v, int m) { return m >= 16 ? v[m - 16] : -v[48 - m]; }
+// the m of the X behind V[i] (V[16] = 0: any)
+__device__ __forceinline__ constexpr int m_of_v(int i) { return i < 16 ? 16 + i : i == 16 ? 0 : i < 48 ? 48 - i : i - 48; }
 // V of an X vector (inverse identity; V[16] = 0).
 // x: one slot of the column-major ring (X[m] at x[kS * kPosOfM[m]], kS the
 // ring's column stride).
@@ -473,7 +485,12 @@ constexpr float kHotS = MP3G_HOT_S;
 // measured within +-1 LSB on those up to |S| = 56 (tools/fast_tolerance.py,
 // spike patterns).  So a granule is hot when max |S| > kHotS (all lines at
 // most 4: per-slot sums <= 128, within +-1 LSB on the adversarial dense
-// patterns) AND some slot's sum exceeds kHotL1 (|X| <= 64 otherwise).
+// patterns) AND some slot's sum exceeds kHotL1.  Otherwise every |X[m]| <=
+// sum_k |S[k]| <= 64, and what the ring holds, X[m] / sigma[m] with
+// 0.707 <= |sigma| <= 1, is at most 64 / 0.707 = 90.5: the quotient the
+// window multiplies by a tap that carries sigma, so each product, and the
+// error it brings, is that of the unscaled |X| <= 64 up to one more rounding
+// of the tap (the adversarial patterns at kHotS measure it: still 1 LSB).
 #ifndef MP3G_HOT_L1
 #define MP3G_HOT_L1 64.0f
 #endif
@@ -902,71 +919,6 @@ __device__ __forceinline__ int imdct_block_type(uint32_t d1, int k) {
   return bt;
 }
 
-// IMDCT + overlap + frequency inversion in fast order: raw[0..17] + old
-// overlap -> o[], raw[18..35] -> new overlap, frequency inversion riding on
-// the signs of the windows and of stp.
-__device__ __forceinline__ void imdct_fast(const float x[18], int bt, int nch, bool act, float sodd,
-                                           const SharedSmem& sh, f2 stp[9], float o[18]) {
-  if (bt == 2) {
-    float st[18];
-#pragma unroll
-    for (int q = 0; q < 9; q++) {
-      st[q] = stp[q].x;
-      st[17 - q] = stp[q].y;
-    }
-    // raw[pos] = sum over the windows wi with 0 <= pos-6-6wi < 12 of
-    // (sum_m x[wi+3m] cosN12[m][p]) * win[2][p], p = pos-6-6wi (imdct.go:88-94)
-#pragma unroll
-    for (int pos = 0; pos < 36; pos++) {
-      float raw = 0.0f;
-#pragma unroll
-      for (int wi = 0; wi < 3; wi++) {
-        const int p = pos - 6 - 6 * wi;
-        if (p < 0 || p >= 12) continue;
-        float sum = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 6; m++) sum += x[wi + 3 * m] * dct4::kCos12[p][m];
-        raw += sum * dct4::kWin12[p];
-      }
-      if (pos & 1) raw *= sodd;  // (pos and pos - 18 have the same parity)
-      if (pos < 18) o[pos] = raw + st[pos];
-      else st[pos - 18] = self(act, raw, st[pos - 18]);
-    }
-#pragma unroll
-    for (int q = 0; q < 9; q++) stp[q] = (f2){st[q], st[17 - q]};
-  } else {
-    // the 18 distinct sums are a DCT-IV of size 18 (dct4_18.h):
-    // sum_m x[m] cosN36[m][q] = X[9+q], sum_m x[m] cosN36[m][18+q] = -X[8-q];
-    // packed, pair k = (X[2k], X[17-2k]) holds X[9+q] and X[8-q] of one q
-    f2 P[9];
-    dct4::dct4_18_pk(x, P);
-    const float4* Wq = sh.winp[bt][lane_fresh() & 1];
-    // (the overlap of an absent channel stays frozen: frame.go Decode
-    // touches ch < nch only; stereo granules need no per-lane select)
-    auto overlap = [&](auto frozen) {
-#pragma unroll
-      for (int kk = 0; kk < 9; kk++) {
-        const int q = kk <= 4 ? 8 - 2 * kk : 2 * kk - 9;
-        const float za = kk <= 4 ? P[kk].y : P[kk].x;  // X[9+q]
-        const float zb = kk <= 4 ? P[kk].x : P[kk].y;  // X[8-q]
-        const float4 w = Wq[q];
-        // (o[q], o[17-q]) = X[9+q] (W[q], -W[17-q]) + stp[q];
-        // new stp[q] = X[8-q] (-W[18+q], -W[35-q])   (signs folded in w)
-        const f2 oq = pfma(bcast(za), (f2){w.x, w.y}, stp[q]);
-        o[q] = oq.x;
-        o[17 - q] = oq.y;
-        const f2 ns = bcast(zb) * (f2){w.z, w.w};
-        if constexpr (decltype(frozen)::value)
-          stp[q] = (f2){self(act, ns.x, stp[q].x), self(act, ns.y, stp[q].y)};
-        else
-          stp[q] = ns;
-      }
-    };
-    if (nch == 2) overlap(std::false_type{});
-    else overlap(std::true_type{});
-  }
-}
-
 // Entry state of a replay start: overlap store in registers, V history as X
 // vectors, from the stream's state_in (init_in) or zero.  stp[q] =
 // (store[q], store[17-q]), each element times the frequency-inversion sign of
@@ -1147,11 +1099,22 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       const float* W = g_fast.win[bt];
       // frequency inversion: line j of an odd subband is negated when j is odd
       const float sq = par && (q & 1) ? -1.0f : 1.0f, sr = par && !(q & 1) ? -1.0f : 1.0f;  // j = q, 17 - q
-      sh.winp[bt][par][q] = make_float4(W[q] * sq, -W[17 - q] * sr, -W[18 + q] * sq, -W[35 - q] * sr);
+      // the long windows also take the factors the scaled DCT-IV-18 leaves out
+      // (dct4_18.h): (.x, .y) multiply X[9+q], (.z, .w) multiply X[8-q]; the
+      // short-block path (bt 2) reads neither this row nor that transform
+      const float fa = bt == 2 ? 1.0f : dct4::kScaleX(9 + q), fb = bt == 2 ? 1.0f : dct4::kScaleX(8 - q);
+      sh.winp[bt][par][q] = make_float4(W[q] * sq * fa, -W[17 - q] * sr * fa, -W[18 + q] * sq * fb, -W[35 - q] * sr * fb);
     }
     // is_pos 0..6 -> isRatios (frame.go:304-306); 7 -> (1, 1): no change
     for (int e = t; e < 16; e += kLanes * kWaves) (&sh.isr[0][0])[e] = e < 14 ? (&g_fast.is_ratio[0][0])[e] : 1.0f;
-    for (int e = t; e < 32 * 16; e += kLanes * kWaves) sh.dwin[e >> 4][e & 15] = (&g_fast.dwin[0][0])[e] * 32767.0f;
+    // the ring holds X[m] / sigma[m] (dct32::kScale, the scaled matrixing):
+    // lane i's even taps read X[ma(i)] (column pa) and its odd taps X[mb(i)]
+    // (column pb), so each tap takes the sigma of the value it multiplies
+    for (int e = t; e < 32 * 16; e += kLanes * kWaves) {
+      const int i = e >> 4, j = e & 15;
+      const int m = (j & 1) ? (i < 16 ? 16 - i : i - 16) : (i < 16 ? 16 + i : (i == 16 ? 0 : 48 - i));
+      sh.dwin[i][j] = (&g_fast.dwin[0][0])[e] * 32767.0f * dct32::kScale[m];
+    }
     for (int e = t; e < kCombos * 32; e += kLanes * kWaves) {
       const uint32_t lb = (&g_fast.lband[0][0])[e];
       uint32_t d = 0;
@@ -1212,7 +1175,9 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     for (int e = lane; e < 2 * 15 * 32; e += kLanes) {
       const int c = e / (15 * 32), blk = (e >> 5) % 15, m = e & 31;
       const bool in = c ? in1 : in0;
-      s.ring[c][dct32::kPosOfM[m]][kHist - 1 - blk] = in ? x_from_v(&sin->vvec[c][64 * blk], m) : 0.0f;
+      // (the ring holds X / sigma, dct32::kScale: the state stays in the V domain)
+      s.ring[c][dct32::kPosOfM[m]][kHist - 1 - blk] =
+          in ? x_from_v(&sin->vvec[c][64 * blk], m) * dct32::kInvScale[m] : 0.0f;
     }
   }
 
@@ -1395,6 +1360,10 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     // this lane's channel (lanes of an absent channel mirror channel 0's block
     // layout: no extra divergence)
     const uint32_t d0 = (act && ch) ? cp0[1] : cp0[0], d1 = (act && ch) ? cp1[1] : cp1[0];
+    // MS stereo over every line (long blocks, no intensity stereo; wave-
+    // uniform): its 1/sqrt2 goes into the band gains, 2^(n4/4 - 1/2)
+    const bool ms_all = all_long && nch == 2 && hdr_mode(h) == 1 && (h & 0x30u) == 0x20u;
+    const float ms_off = ms_all ? -0.5f : 0.0f;
 
     // ---- per-granule front-end parameters: band exponents (long bands only
     //      when no channel has short blocks) ----
@@ -1409,7 +1378,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
         const int sfb = e & 31;
         const int v = (int)((d0 >> 16) & 0xffu) - 210 -
                       ((d0 >> 24) ? 4 : 2) * (sfl_byte + (int)(d1 & 0xffu) * kPretab(sfb));
-        if (all_long) s.expo_gain()[22 * ch + sfb] = __builtin_amdgcn_exp2f(0.25f * (float)v);
+        if (all_long) s.expo_gain()[22 * ch + sfb] = __builtin_amdgcn_exp2f(__builtin_fmaf(0.25f, (float)v, ms_off));
         else s.expo[22 * ch + sfb] = (_Float16)(0.25f * (float)v);
       }
       if (!all_long) {
@@ -1577,23 +1546,25 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
         // stereo transform every line: at or above max(count1) both channels
         // are 0, where (l +- r)c is 0 too.  Otherwise lines >= max(count1) keep
         // their values (the reorder can move values past count1; IS follows).
-        auto ms_pair = [&](float& u, float& v) {
+        // (gained: the band gains of this granule carry the 1/sqrt2 already)
+        auto ms_pair = [&](float& u, float& v, auto gained) {
           const auto r = __builtin_amdgcn_permlane32_swap(__float_as_int(u), __float_as_int(v), false, false);
           const float a = __int_as_float(r[0]), b = __int_as_float(r[1]);
-          const f2 pq = (f2){a + b, a - b} * bcast(inv_sqrt2);
+          f2 pq = (f2){a + b, a - b};
+          if constexpr (!decltype(gained)::value) pq = pq * bcast(inv_sqrt2);
           const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_int(pq.x), __float_as_int(pq.y), false, false);
           u = __int_as_float(r2[0]);
           v = __int_as_float(r2[1]);
         };
-        if (all_long && !is) {  // wave-uniform
+        if (all_long && !is) {  // wave-uniform (ms_all)
 #pragma unroll
-          for (int j = 0; j < 18; j += 2) ms_pair(x[j], x[j + 1]);
+          for (int j = 0; j < 18; j += 2) ms_pair(x[j], x[j + 1], std::true_type{});
         } else {
           const int left = msmax - 18 * (lane_fresh() & 31);  // lines of this subband below msmax
 #pragma unroll
           for (int j = 0; j < 18; j += 2) {
             float n0 = x[j], n1 = x[j + 1];
-            ms_pair(n0, n1);
+            ms_pair(n0, n1, std::false_type{});
             x[j] = j < left ? n0 : x[j];
             x[j + 1] = j + 1 < left ? n1 : x[j + 1];
           }
@@ -1705,9 +1676,11 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       } else {
         // the 18 distinct sums are a DCT-IV of size 18 (dct4_18.h):
         // sum_m x[m] cosN36[m][q] = X[9+q], sum_m x[m] cosN36[m][18+q] = -X[8-q];
-        // packed, pair k = (X[2k], X[17-2k]) holds X[9+q] and X[8-q] of one q
+        // packed, pair k = (X[2k], X[17-2k]) holds X[9+q] and X[8-q] of one q --
+        // each short of its post-twiddle's factor (dct4_18_pk_scaled), which
+        // shared_init put into winp: both products below multiply by it
         f2 P[9];
-        dct4::dct4_18_pk(x, P);
+        dct4::dct4_18_pk_scaled(x, P);
         const float4* Wq = sh.winp[bt][lane_fresh() & 1];
         // (the overlap of an absent channel stays frozen: frame.go Decode
         // touches ch < nch only; stereo granules need no per-lane select)
@@ -1804,7 +1777,8 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
         dct32::f2 sp[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) sp[q] = (dct32::f2){colu[kSlots * 2 * q], colu[kSlots * (2 * q + 1)]};
-        dct32::dct2_32_to(sp, [&](int t, dct32::f2 v) {
+        // (X[m] / sigma[m]: the window's taps in sh.dwin carry sigma)
+        dct32::dct2_32_scaled_to(sp, [&](int t, dct32::f2 v) {
           colu[kSlots * dct32::kColX[t]] = v.x;
           colu[kSlots * dct32::kColY[t]] = v.y;
         });
@@ -1867,7 +1841,8 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
   // Frame.store / vVec after the chunk's last granule (frame.go:48-49); Pn:
   // the layout the next granule would have used, whose history the last 15 V
   // blocks are
-  auto export_state = [&](const f2 (&st)[9], uint32_t Pn) {
+  // (scaled: the ring holds X / sigma, the fast loop's; the state is V itself)
+  auto export_state = [&](const f2 (&st)[9], uint32_t Pn, bool scaled) {
     if (!(cd.flags & kChunkStateOut)) return;
     mp3g_state* so = state_out + cd.stream;
     const int c = lane_fresh() >> 5, kk = lane_fresh() & 31;
@@ -1880,11 +1855,12 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     for (int e = lane_fresh(); e < 2 * 1024; e += kLanes) {
       const int cc = e >> 10, blk = (e >> 6) & 15, i = e & 63;
       const int z = kHist - 1 - blk;  // (blk < 15: a history slot)
-      so->vvec[cc][64 * blk + i] = blk < 15 ? v_from_x(&s.ring[cc][0][0] + (Pn ? 18 + z : z), i) : 0.0f;
+      const float sig = scaled ? dct32::kScale[m_of_v(i)] : 1.0f;
+      so->vvec[cc][64 * blk + i] = blk < 15 ? v_from_x(&s.ring[cc][0][0] + (Pn ? 18 + z : z), i) * sig : 0.0f;
     }
   };
   static_assert(rphys(1, 1) == 19 && rphys(1, 15) == 33 && rphys(0, 15) == 15, "export_state's history positions");
-  export_state(stp, lay & 1u);
+  export_state(stp, lay & 1u, true);
 
   // ---- hot zones (rare): redo their granules in the reference's order from
   //      their replay start (exact entry state) and overwrite their PCM; a
@@ -2004,7 +1980,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       }
       done = gz;
     }
-    if (done >= end) export_state(zst, 0u);  // (the zone pass keeps layout E: init_state, exact_granule)
+    if (done >= end) export_state(zst, 0u, false);  // (the zone pass keeps layout E: init_state, exact_granule)
     // (rare: one vector atomic per counter from lane 0 of a chunk with zones)
     if (kHotCount && hot_count && lane_fresh() == 0) {
       atomicAdd(hot_count + 0, n_out);

@@ -128,6 +128,39 @@ MP3G_PK f2 post_tw(f2 v, float c, float s) {
   return fma2(bhi(v), mk(s, -c), blo(v) * mk(c, s));
 #endif
 }
+// The scaled post-twiddle: post_tw(v, c, s) / post_scale(c, s), for a reader
+// that folds the factor into a table it multiplies by anyway.  The larger of
+// (c, s) comes out, so the remaining coefficient t = min / max is <= 1 and
+// the bracket is one instruction:
+//   c >= s: c (vr + t vi, t vr - vi)      c == s: s (vr + vi, vr - vi)
+//   c <  s: s (t vr + vi, vr - t vi)
+// (c, s >= 0: the transforms' post-twiddles are first-quadrant.)
+constexpr float post_scale(float c, float s) { return c >= s ? c : s; }
+constexpr float post_ratio(float c, float s) { return c >= s ? (float)((double)s / c) : (float)((double)c / s); }
+MP3G_PK f2 post_tw_s(f2 v, float c, float s) {
+  const float t = post_ratio(c, s);
+#if defined(__HIP_DEVICE_COMPILE__)
+  f2 r;
+  if (c == s) {
+    asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[1,0]" : "=v"(r) : "v"(v));  // (vr + vi, -vi + vr)
+  } else if (c > s) {
+    const uint64_t tt = cpair(t, t);
+    asm("v_pk_fma_f32 %0, %1, %2, %1 op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_hi:[0,0,1]"  // (vi t + vr, vr t - vi)
+        : "=v"(r)
+        : "v"(v), "s"(tt));
+  } else {
+    const uint64_t tt = cpair(t, t);
+    asm("v_pk_fma_f32 %0, %1, %2, %1 op_sel:[0,0,1] op_sel_hi:[1,1,0] neg_hi:[0,1,0]"  // (vr t + vi, -vi t + vr)
+        : "=v"(r)
+        : "v"(v), "s"(tt));
+  }
+  return r;
+#else
+  if (c == s) return mk(v.x + v.y, v.x - v.y);
+  if (c > s) return fma2(swp(v), mk(t, t), mk(v.x, -v.y));
+  return fma2(v, mk(t, -t), swp(v));
+#endif
+}
 
 }  // namespace pk
 }  // namespace mp3g
