@@ -189,6 +189,22 @@ def lib():
             L.mp3g_mfcc_execute.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
             L.mp3g_cmvn_rows.argtypes = [C.c_int, vp, u32, u32, u32, u32, u32, vp, u32, vp]
             L.mp3g_cmvn_host.argtypes = [vp, u32, u32, u32, u32, u32, vp, u32]
+        if hasattr(L, "mp3g_loudness_create"):
+            dp = C.POINTER(vp)
+            L.mp3g_loudness_create.argtypes = [C.c_int, C.c_int, dp]
+            L.mp3g_loudness_free.argtypes = [vp]
+            L.mp3g_loudness_free.restype = None
+            L.mp3g_loudness_info.argtypes = [vp, C.POINTER(u32), dp, dp, dp, dp, dp]
+            L.mp3g_loudness_blocks.argtypes = [vp, u64]
+            L.mp3g_loudness_blocks.restype = u64
+            L.mp3g_loudness_host.argtypes = [vp, vp, u32, u32, u32, vp, vp]
+            L.mp3g_loudness_scratch_bytes.argtypes = [vp, u32, u32, u32]
+            L.mp3g_loudness_scratch_bytes.restype = u64
+            L.mp3g_loudness_rows.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]
+            L.mp3g_loudness_target_energy.argtypes = [C.c_double]
+            L.mp3g_loudness_target_energy.restype = C.c_double
+            L.mp3g_gain_rows.argtypes = [C.c_int, vp, u32, u32, u32, vp, vp, C.c_double, C.c_float, vp, vp]
+            L.mp3g_gain_host.argtypes = [vp, u32, u32, u32, vp, vp, C.c_double, C.c_float, vp]
         L.mp3g_lame_parse.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo)]
         L.mp3g_lame_parse_reader.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo), C.POINTER(C.c_size_t)]
         L.mp3g_lame_total_delay.argtypes = [C.POINTER(_LameInfo)]
@@ -1328,6 +1344,264 @@ def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_lengt
     finally:
         mf.close()
     return feats, flen, end_status, rates
+
+
+# ---- integrated loudness of decoded rows (include/mp3g.h) -----------------------
+# one record per row (mp3g_loudness_stats)
+LOUDNESS_STATS_DTYPE = np.dtype([("energy", "<f8"), ("lufs", "<f4"), ("peak", "<f4"), ("n_blocks", "<u4"),
+                                 ("n_abs", "<u4"), ("n_gated", "<u4"), ("zero", "<u4")])
+assert LOUDNESS_STATS_DTYPE.itemsize == 32
+LOUDNESS_ABS_GATE = 1.1724653045822964e-07
+
+
+def loudness_target_energy(lufs):
+    """The mean gated block energy of `lufs`: 10^((lufs + 0.691) / 10)
+    (mp3g_loudness_target_energy)."""
+    return float(lib().mp3g_loudness_target_energy(float(lufs)))
+
+
+def _device_lengths(lengths, B, device, what):
+    """One length per row as an int32 device tensor (None stays None; values
+    above the row length mean the row length)."""
+    import torch
+    if lengths is None:
+        return None
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        d = lengths.to(torch.int32).contiguous()
+    else:
+        host = np.ascontiguousarray(np.clip(np.asarray(lengths, dtype=np.int64), 0, 2 ** 31 - 1), dtype=np.int32)
+        d = torch.from_numpy(host).to(device)
+    if tuple(d.shape) != (B,):
+        raise ValueError(what + ": one length per row")
+    return d
+
+
+class Loudness:
+    """ITU-R BS.1770-4 integrated loudness and the sample peak of float32 rows
+    at `rate` (8000 .. 192000 Hz; mp3g_loudness_*): K-weighting, 400 ms blocks
+    every H = (rate + 5) // 10 samples, the absolute gate at -70 LUFS and the
+    relative gate 10 LU under the mean.  One or two planes, each of weight 1.
+    The filter runs per 100 ms segment from zero state and a scan over the
+    segments adds what the carried-in state contributes, all in float64 in one
+    fixed order, so the device call (execute) equals the host reference (host)
+    byte for byte.  shelf and highpass are the two sections as b0 b1 b2 a1 a2;
+    V [H, 4], AH [4, 4] and G [4, 4] the segment tables.  Momentary and
+    short-term loudness, loudness range and true peak are not offered.
+    device=None (or -1) makes a host-only object."""
+
+    def __init__(self, rate, device=None):
+        self._h = C.c_void_p()
+        self.device = -1 if device is None else int(device)
+        self.rate = int(rate)
+        _check(lib().mp3g_loudness_create(self.device, self.rate, C.byref(self._h)))
+        h = C.c_uint32()
+        p = [C.c_void_p() for _ in range(5)]
+        _check(lib().mp3g_loudness_info(self._h, C.byref(h), *[C.byref(q) for q in p]))
+        self.H = h.value
+
+        def view(q, shape):  # a view of the library's table: valid while this object lives
+            return np.ctypeslib.as_array(C.cast(q, C.POINTER(C.c_double)), shape=shape)
+        self.shelf, self.highpass = view(p[0], (5,)), view(p[1], (5,))
+        self.V, self.AH, self.G = view(p[2], (self.H, 4)), view(p[3], (4, 4)), view(p[4], (4, 4))
+        self._scratch = self._keep = None
+
+    def blocks(self, n):
+        """The 400 ms blocks a row of n samples has (mp3g_loudness_blocks)."""
+        return int(lib().mp3g_loudness_blocks(self._h, int(n)))
+
+    def host(self, x, lengths=None):
+        """The reference on the CPU (mp3g_loudness_host): x float32 [B, C, T]
+        (C = 1 or 2) or [B, T]; lengths: one sample count per row (None: T).
+        Returns LOUDNESS_STATS_DTYPE[B]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim not in (2, 3):
+            raise ValueError("Loudness.host: x is [B, C, T] or [B, T]")
+        B, T = x.shape[0], x.shape[-1]
+        planes = x.shape[1] if x.ndim == 3 else 1
+        ln = None
+        if lengths is not None:
+            ln = np.ascontiguousarray(np.clip(np.asarray(lengths, dtype=np.int64), 0, 2 ** 32 - 1), dtype=np.uint32)
+            if ln.shape != (B,):
+                raise ValueError("Loudness.host: one length per row")
+        stats = np.zeros(B, LOUDNESS_STATS_DTYPE)
+        _check(lib().mp3g_loudness_host(self._h, _ptr(x) if x.size else None, B, planes, T,
+                                        _ptr(ln) if ln is not None and B else None, _ptr(stats) if B else None))
+        return stats
+
+    def execute(self, d_src, lengths=None, rows=None, stream=None, d_stats=None):
+        """The device call (mp3g_loudness_rows): d_src float32 [B, C, T] (C = 1
+        or 2) or [B, T], contiguous on this object's device; lengths: one
+        sample count per row (a device tensor or array-like; None: T); rows: the
+        rows to measure (array-like or an int32 device tensor; None: all).
+        Returns the records as a uint8 device tensor [B, 32] (d_stats when
+        given, else a new zero-filled one): only the records of the measured
+        rows are written.  The scratch is a tensor this object keeps and grows.
+        Two launches, asynchronous on `stream` (a hipStream_t; None = the
+        current torch stream); read the records with stats()."""
+        import torch
+        if d_src.dtype != torch.float32 or not d_src.is_contiguous() or d_src.dim() not in (2, 3) or not d_src.is_cuda:
+            raise ValueError("Loudness.execute: a contiguous float32 device tensor [B, C, T] or [B, T]")
+        B, T = int(d_src.shape[0]), int(d_src.shape[-1])
+        planes = int(d_src.shape[1]) if d_src.dim() == 3 else 1
+        dev = d_src.device
+        if d_stats is None:
+            d_stats = torch.zeros((B, LOUDNESS_STATS_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        if (d_stats.dtype != torch.uint8 or not d_stats.is_contiguous() or not d_stats.is_cuda
+                or tuple(d_stats.shape) != (B, LOUDNESS_STATS_DTYPE.itemsize)):
+            raise ValueError("Loudness.execute: d_stats is a contiguous uint8 device tensor [B, 32]")
+        d_len = _device_lengths(lengths, B, dev, "Loudness.execute")
+        d_rows, n_index = None, 0
+        if rows is not None:
+            if torch.is_tensor(rows) and rows.is_cuda:
+                d_rows = rows.to(torch.int32).contiguous()
+            else:
+                host = np.ascontiguousarray(rows, dtype=np.int64)
+                if host.ndim != 1 or (len(host) and (host.min() < 0 or host.max() >= B)):
+                    raise ValueError("Loudness.execute: rows lie in [0, B)")
+                d_rows = torch.from_numpy(host.astype(np.int32)).to(dev)
+            n_index = int(d_rows.numel())
+            if n_index > B:
+                raise ValueError("Loudness.execute: more rows than the batch has")
+            if n_index == 0:
+                return d_stats
+        need = int(lib().mp3g_loudness_scratch_bytes(self._h, B, planes, T))
+        if B and need == 0:
+            _check(lib().mp3g_loudness_rows(self._h, None, B, planes, T, None, None, 0, None, None, None))
+        if self._scratch is None or self._scratch.numel() * 8 < need or self._scratch.device != dev:
+            self._scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+        self._keep = (d_len, d_rows)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def p(t):
+            return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+        _check(lib().mp3g_loudness_rows(self._h, p(d_src), B, planes, T, p(d_len), p(d_rows), n_index,
+                                        p(self._scratch), p(d_stats), C.c_void_p(stream) if stream else None))
+        return d_stats
+
+    @staticmethod
+    def stats(t):
+        """The records of execute() as a numpy LOUDNESS_STATS_DTYPE array
+        (synchronises with the device)."""
+        return t.cpu().numpy().reshape(-1).view(LOUDNESS_STATS_DTYPE).copy()
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.shelf = self.highpass = self.V = self.AH = self.G = None
+            self._scratch = self._keep = None
+            lib().mp3g_loudness_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def loudness_gain_host(x, stats, target_lufs, peak_ceiling=None, lengths=None):
+    """The reference on the CPU (mp3g_gain_host): (y, gains) with y a copy of
+    the float32 array x [B, C, T] or [B, T] whose row b is multiplied over its
+    first min(lengths[b], T) samples by gains[b] = float32(sqrt(target energy /
+    stats[b].energy)), capped at peak_ceiling / stats[b].peak when a ceiling is
+    given; a row of energy 0 is copied and has gain 1."""
+    y = np.array(x, dtype=np.float32, order="C", copy=True)
+    if y.ndim not in (2, 3):
+        raise ValueError("loudness_gain_host: x is [B, C, T] or [B, T]")
+    B, T = y.shape[0], y.shape[-1]
+    planes = y.shape[1] if y.ndim == 3 else 1
+    stats = np.ascontiguousarray(stats, dtype=LOUDNESS_STATS_DTYPE)
+    if stats.shape != (B,):
+        raise ValueError("loudness_gain_host: one record per row")
+    ln = None
+    if lengths is not None:
+        ln = np.ascontiguousarray(np.clip(np.asarray(lengths, dtype=np.int64), 0, 2 ** 32 - 1), dtype=np.uint32)
+        if ln.shape != (B,):
+            raise ValueError("loudness_gain_host: one length per row")
+    gains = np.ones(B, np.float32)
+    _check(lib().mp3g_gain_host(_ptr(y) if y.size else None, B, planes, T, _ptr(ln) if ln is not None and B else None,
+                                _ptr(stats) if B else None, loudness_target_energy(target_lufs),
+                                0.0 if peak_ceiling is None else float(peak_ceiling), _ptr(gains) if B else None))
+    return y, gains
+
+
+def loudness_gain(d_x, d_stats, target_lufs, peak_ceiling=None, lengths=None, stream=None):
+    """The device call (mp3g_gain_rows): multiplies the contiguous float32
+    device tensor d_x [B, C, T] or [B, T] in place, row b over its first
+    min(lengths[b], T) samples, by the gain that brings the loudness d_stats
+    (Loudness.execute's records) reports to target_lufs, capped so that the
+    sample peak stays at or below peak_ceiling when one is given -- as
+    loudness_gain_host states it and bit for bit.  One launch, asynchronous on
+    `stream` (a hipStream_t; None = the current torch stream).  Returns the
+    gains, a float32 device tensor [B]."""
+    import torch
+    if (not torch.is_tensor(d_x) or d_x.dtype != torch.float32 or not d_x.is_contiguous() or not d_x.is_cuda
+            or d_x.dim() not in (2, 3)):
+        raise ValueError("loudness_gain: a contiguous float32 device tensor [B, C, T] or [B, T]")
+    B, T = int(d_x.shape[0]), int(d_x.shape[-1])
+    planes = int(d_x.shape[1]) if d_x.dim() == 3 else 1
+    if (not torch.is_tensor(d_stats) or d_stats.dtype != torch.uint8 or not d_stats.is_contiguous()
+            or d_stats.device != d_x.device or tuple(d_stats.shape) != (B, LOUDNESS_STATS_DTYPE.itemsize)):
+        raise ValueError("loudness_gain: d_stats is a contiguous uint8 tensor [B, 32] on d_x's device")
+    d_len = _device_lengths(lengths, B, d_x.device, "loudness_gain")
+    gains = torch.empty(B, dtype=torch.float32, device=d_x.device)  # (every row's gain is written)
+    if stream is None:
+        stream = torch.cuda.current_stream(d_x.device).cuda_stream
+    _check(lib().mp3g_gain_rows(d_x.device.index or 0, C.c_void_p(d_x.data_ptr()) if d_x.numel() else None, B, planes,
+                                T, C.c_void_p(d_len.data_ptr()) if d_len is not None and B else None,
+                                C.c_void_p(d_stats.data_ptr()) if B else None, loudness_target_energy(target_lufs),
+                                0.0 if peak_ceiling is None else float(peak_ceiling),
+                                C.c_void_p(gains.data_ptr()) if B else None, C.c_void_p(stream) if stream else None))
+    return gains
+
+
+def decode_windows_normalized_tensor(datas, starts, n_samples, target_lufs=-23.0, peak_ceiling=None, rate=None,
+                                     mode=MODE_EXACT, out_format=OUT_F32_PLANAR, gapless=False, quality="fast",
+                                     n_threads=0, device=0):
+    """A windowed decode, its loudness and the gain to target_lufs, all on the
+    GPU.  rate=None: decode_windows_tensor, each row measured at its stream's
+    own rate (stream_rates; one Loudness and one measurement per distinct
+    rate); with a rate: decode_windows_resampled_tensor and one Loudness(rate).
+    Every row is measured over its own samples (lengths) and then multiplied in
+    place by loudness_gain; target_lufs=None measures only and leaves the batch
+    as decoded.  The loudness is that of the WINDOW: a caller who wants a
+    file's loudness passes a window that covers the file.  A stream with no
+    valid frame is an all-zero row with lufs = -inf and gain 1.
+
+    Returns what the underlying call returns -- (batch, lengths, end_status)
+    or (batch, lengths, end_status, rates) -- followed by stats
+    (LOUDNESS_STATS_DTYPE[B], numpy: Loudness.host of the un-normalised batch
+    byte for byte) and gains (float32[B], numpy; ones when only measuring)."""
+    import torch
+    B = len(datas)
+    if rate is None:
+        res = decode_windows_tensor(datas, starts, n_samples, mode=mode, out_format=out_format, gapless=gapless,
+                                    n_threads=n_threads, device=device)
+        row_rates = stream_rates(datas, n_threads=n_threads)
+    else:
+        res = decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=mode, out_format=out_format,
+                                              gapless=gapless, quality=quality, n_threads=n_threads, device=device)
+        row_rates = np.where(res[3] > 0, int(rate), 0)
+    batch, lengths = res[0], res[1]
+    # a row no Loudness measures keeps this record: the zero row's
+    blank = np.zeros(B, LOUDNESS_STATS_DTYPE)
+    blank["lufs"] = -np.inf
+    d_stats = torch.from_numpy(blank.view(np.uint8).reshape(B, -1).copy()).to(batch.device)
+    d_len = torch.from_numpy(np.ascontiguousarray(lengths, dtype=np.int32)).to(batch.device)
+    meters = {int(f): Loudness(int(f), device=device) for f in set(row_rates.tolist()) if f}
+    try:
+        for f, m in meters.items():
+            m.execute(batch, lengths=d_len, rows=np.nonzero(row_rates == f)[0], d_stats=d_stats)
+        gains = None
+        if target_lufs is not None and B:
+            gains = loudness_gain(batch, d_stats, target_lufs, peak_ceiling=peak_ceiling, lengths=d_len)
+        torch.cuda.current_stream(batch.device).synchronize()
+    finally:
+        for m in meters.values():
+            m.close()
+    stats = Loudness.stats(d_stats)
+    gains = np.ones(B, np.float32) if gains is None else gains.cpu().numpy()
+    return tuple(res) + (stats, gains)
 
 
 # ---- STFT and mel spectrograms of decoded rows (include/mp3g.h) ----------------

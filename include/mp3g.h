@@ -57,7 +57,9 @@ extern "C" {
  *    Kaldi filter-bank features of decoded rows -- mp3g_fbank_*; STFT and mel
  *    spectrograms of decoded rows -- mp3g_stft_*; Kaldi MFCC features of
  *    decoded rows -- mp3g_mfcc_*; per-row mean and variance normalisation --
- *    mp3g_cmvn_rows and mp3g_cmvn_host.) */
+ *    mp3g_cmvn_rows and mp3g_cmvn_host; BS.1770 integrated loudness of decoded
+ *    rows and the gain stage -- mp3g_loudness_*, mp3g_gain_rows and
+ *    mp3g_gain_host.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -901,6 +903,97 @@ int mp3g_cmvn_rows(int device, float* d_feats, uint32_t n_rows, uint32_t n_plane
                    uint32_t stride, uint32_t n_cols, const uint32_t* d_lengths, uint32_t flags, void* hip_stream);
 int mp3g_cmvn_host(float* feats, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames, uint32_t stride,
                    uint32_t n_cols, const uint32_t* lengths, uint32_t flags);
+
+/* ---- Integrated loudness of decoded rows ----------------------------------------
+ * ITU-R BS.1770-4 integrated loudness (what libebur128, pyloudnorm and ffmpeg's
+ * loudnorm report as "I") and the sample peak of every row of a batch
+ * float [n_rows][n_planes][T], n_planes 1 or 2, and a gain stage that brings the
+ * rows to a target.  Both planes have channel weight 1; a mono row is one
+ * channel.  NOT offered: momentary and short-term loudness, loudness range,
+ * true peak (the 4x oversampled kind), surround channel weights.
+ *
+ * mp3g_loudness_create(device, rate): rate 8000 .. 192000 (outside:
+ * MP3G_ERR_UNSUPPORTED; rate <= 0 or a null pointer: MP3G_ERR_INVALID_ARGUMENT;
+ * both with *out = NULL before any device call); device = -1 makes a host-only
+ * object.  The K-weighting is two biquads designed in float64 from the analog
+ * prototypes, as libebur128 and pyloudnorm design them (a0 = 1):
+ *   shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196
+ *     K = tan(pi f0 / rate), Vh = 10^(G/20), Vb = Vh^0.4996667741545416,
+ *     a0 = 1 + K/Q + K^2;  b = [Vh + Vb K/Q + K^2, 2 (K^2 - Vh), Vh - Vb K/Q + K^2] / a0
+ *     a = [1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0]
+ *   high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, K and a0 alike;
+ *     b = [1, -2, 1] (not normalised), a as above
+ * (at 48 kHz the standard's printed table).  H = (rate + 5) / 10 in integers is
+ * the 100 ms segment; a block is 4 H samples, the step H.  The filter state is
+ * four doubles: the shelf's two, then the high-pass's two, transposed direct
+ * form II.  From the filter code itself run on zero input from each unit state
+ * e_k: V[n][k] the output at sample n < H, AH[m][k] the state after H samples,
+ * G[a][b] = sum_n V[n][a] V[n][b] (n ascending); all float64, [k] fastest.
+ *
+ * The measurement.  len_r = T, or min(lengths[r], T) with lengths;
+ * nseg = len_r / H, n_blocks = nseg >= 4 ? nseg - 3 : 0; samples past nseg H
+ * take part only in the peak.  Everything below is float64 in the operation
+ * order of go-mp3_amd/csrc/loudness_filter.h, without contraction.
+ *   per (row, plane, segment j < nseg), from ZERO state, n ascending over its H
+ *   samples: w[n] the K-weighted sample;  Ezs += w w;  g[k] += V[n][k] w;
+ *   send = the state after the segment
+ *   per (row, plane), j ascending, s0 = 0:
+ *     E_j = max((Ezs_j + 2 (g_j . s0)) + s0^T G s0, 0);   s0 = AH s0 + send_j
+ *   -- by superposition the sequential filter's segment energies, up to rounding
+ *   per row: z_i = (sum over planes of ((E_i + E_i+1) + E_i+2) + E_i+3) / (4 H)
+ *     absolute gate: z_i >= Ga = MP3G_LOUDNESS_ABS_GATE (-70 LUFS);
+ *     relative gate: Gr = 0.1 (sum of the z_i >= Ga / n_abs);  a block counts when
+ *     z_i >= Ga and z_i >= Gr;  energy = sum of those z_i / n_gated (i ascending)
+ *     lufs = -0.691f + 10.0f * mp3g_log10f((float)energy); no gated block:
+ *     energy = 0 and lufs = -inf
+ *     peak = max |x[n]| over n < len_r and all planes: the sample peak
+ * One record per row, mp3g_loudness_stats (32 bytes).  mp3g_loudness_host runs
+ * exactly this decomposition, not a sequential filter, and mp3g_loudness_rows
+ * equals it byte for byte.
+ *
+ * mp3g_loudness_rows: d_src, d_lengths (uint32 [n_rows], may be NULL), d_row_index
+ * (uint32 [n_index] rows to measure, may be NULL: all n_rows; values >= n_rows
+ * are skipped), d_scratch (mp3g_loudness_scratch_bytes, 8-byte aligned) and
+ * d_stats ([n_rows] records) are device pointers.  Two launches whose shapes
+ * depend on no device content, no allocation, asynchronous on hip_stream and
+ * graph-capturable; writes the records of the rows it was given and its
+ * scratch, nothing else.  A batch of mixed source rates is measured by one call
+ * per rate through d_row_index.
+ *
+ * The gain stage, in place: per row g = (float)sqrt(target_energy / energy) (a
+ * double division and square root, rounded once); with peak_ceiling > 0 and
+ * peak > 0, g = min(g, peak_ceiling / peak) (a float32 division); energy == 0:
+ * g = 1 and the row is not touched.  y[n] = x[n] * g for n < len_r, nothing else
+ * is written; gain_out[r] = g when the pointer is given.  target_energy =
+ * mp3g_loudness_target_energy(lufs) = 10^((lufs + 0.691) / 10), on the host.
+ * mp3g_gain_rows equals mp3g_gain_host bit for bit; one launch. */
+#define MP3G_LOUDNESS_ABS_GATE 1.1724653045822964e-07 /* the double nearest 10^-6.9309 */
+typedef struct mp3g_loudness mp3g_loudness;
+typedef struct mp3g_loudness_stats {
+  double energy;      /* mean gated block energy; 0: no gated block */
+  float lufs, peak;
+  uint32_t n_blocks, n_abs, n_gated; /* blocks; past the absolute gate; past both */
+  uint32_t zero;
+} mp3g_loudness_stats;
+int mp3g_loudness_create(int device, int rate, mp3g_loudness** out);
+void mp3g_loudness_free(mp3g_loudness* ld);
+/* H and views of the tables (valid while the object lives): shelf and highpass
+ * as b0 b1 b2 a1 a2, V [H][4], AH [4][4], G [4][4].  Any pointer may be NULL. */
+int mp3g_loudness_info(const mp3g_loudness* ld, uint32_t* H, const double** shelf, const double** highpass,
+                       const double** V, const double** AH, const double** G);
+uint64_t mp3g_loudness_blocks(const mp3g_loudness* ld, uint64_t n_samples);
+int mp3g_loudness_host(const mp3g_loudness* ld, const float* x, uint32_t n_rows, uint32_t n_planes, uint32_t T,
+                       const uint32_t* lengths, mp3g_loudness_stats* stats);
+uint64_t mp3g_loudness_scratch_bytes(const mp3g_loudness* ld, uint32_t n_rows, uint32_t n_planes, uint32_t T);
+int mp3g_loudness_rows(const mp3g_loudness* ld, const float* d_src, uint32_t n_rows, uint32_t n_planes, uint32_t T,
+                       const uint32_t* d_lengths, const uint32_t* d_row_index, uint32_t n_index, void* d_scratch,
+                       mp3g_loudness_stats* d_stats, void* hip_stream);
+double mp3g_loudness_target_energy(double lufs);
+int mp3g_gain_rows(int device, float* d_x, uint32_t n_rows, uint32_t n_planes, uint32_t T, const uint32_t* d_lengths,
+                   const mp3g_loudness_stats* d_stats, double target_energy, float peak_ceiling, float* d_gain_out,
+                   void* hip_stream);
+int mp3g_gain_host(float* x, uint32_t n_rows, uint32_t n_planes, uint32_t T, const uint32_t* lengths,
+                   const mp3g_loudness_stats* stats, double target_energy, float peak_ceiling, float* gain_out);
 
 /* ---- STFT and mel spectrograms of decoded rows --------------------------------
  * The front ends of music and general audio at its native rate: an STFT by FFT
