@@ -1006,8 +1006,9 @@ static int16_t pcm_sample(float sum) {
   return (int16_t)v;
 }
 
-/* subbandSynthesis (frame.go:630-688); writes stereo-interleaved int16 */
-static void dsp_synth(int nch, int ch, const float* is, float* vvec, int16_t* out) {
+/* subbandSynthesis (frame.go:630-688); writes stereo-interleaved int16, and to
+ * t_out (when given, same layout) the float32 product pcm_sample truncates */
+static void dsp_synth(int nch, int ch, const float* is, float* vvec, int16_t* out, float* t_out) {
   float u[512], s[32];
   for (int ss = 0; ss < 18; ss++) {
     memmove(&vvec[64], &vvec[0], sizeof(float) * 960);
@@ -1027,6 +1028,11 @@ static void dsp_synth(int nch, int ch, const float* is, float* vvec, int16_t* ou
       for (int j = 0; j < 512; j += 32) sum = sum + u[j + i];
       int16_t smp = pcm_sample(sum);
       int idx = 2 * (32 * ss + i);
+      if (t_out) {
+        float t = sum * 32767.0f;
+        if (nch == 1) t_out[idx] = t_out[idx + 1] = t;
+        else t_out[idx + ch] = t;
+      }
       if (nch == 1) { out[idx] = smp; out[idx + 1] = smp; continue; }
       out[idx + ch] = smp;
     }
@@ -1034,7 +1040,7 @@ static void dsp_synth(int nch, int ch, const float* is, float* vvec, int16_t* ou
 }
 
 static void granule_dsp(uint32_t h, const gc_fields c[2], float is[2][576], float store[2][32][18],
-                        float vvec[2][1024], int16_t* out) {
+                        float vvec[2][1024], int16_t* out, float* t_out) {
   const int* sl = SFB_LONG[fh_lsf(h)][fh_sfreq(h)];
   const int* ss = SFB_SHORT[fh_lsf(h)][fh_sfreq(h)];
   int nch = fh_nch(h);
@@ -1046,7 +1052,7 @@ static void granule_dsp(uint32_t h, const gc_fields c[2], float is[2][576], floa
   for (int ch = 0; ch < nch; ch++) {
     dsp_antialias(&c[ch], is[ch]);
     dsp_hybrid(&c[ch], is[ch], store[ch]);
-    dsp_synth(nch, ch, is[ch], vvec[ch], out);
+    dsp_synth(nch, ch, is[ch], vvec[ch], out, t_out);
   }
 }
 
@@ -1101,40 +1107,63 @@ static void frame_decode(frame_t* f, int16_t* out) {
     gc_fields c[2];
     memset(c, 0, sizeof c);
     for (int ch = 0; ch < nch; ch++) fields_from_frame(f, gr, ch, &c[ch]);
-    granule_dsp(f->header, c, f->md->is[gr], f->store, f->vvec, out + 576 * 2 * gr);
+    granule_dsp(f->header, c, f->md->is[gr], f->store, f->vvec, out + 576 * 2 * gr, NULL);
   }
 }
 
-void orc_dsp_granules(const mp3g_granule* g, const int16_t* coef, size_t n, mp3g_state* st,
-                      int16_t* pcm) {
+/* t_out, when given, receives the pre-truncation products [n][576][2] */
+static void dsp_granules(const mp3g_granule* g, const int16_t* coef, size_t n, mp3g_state* st,
+                         int16_t* pcm, float* t_out) {
   ensure_init();
   float is[2][576];
   for (size_t k = 0; k < n; k++) {
     gc_fields c[2];
     memset(c, 0, sizeof c);
-    int nch = fh_nch(g[k].header);
     for (int ch = 0; ch < 2; ch++) {
       fields_from_desc(&g[k].ch[ch], &c[ch]);
       for (int i = 0; i < 576; i++) is[ch][i] = (float)coef[k * 1152 + ch * 576 + i];
     }
-    (void)nch;
-    granule_dsp(g[k].header, c, is, st->store, st->vvec, pcm + k * 1152);
+    granule_dsp(g[k].header, c, is, st->store, st->vvec, pcm + k * 1152, t_out ? t_out + k * 1152 : NULL);
   }
 }
 
-int orc_dsp_streams(const mp3g_granule* g, const int16_t* coef, const mp3g_stream* streams,
-                    uint32_t n_streams, const mp3g_state* state_in, mp3g_state* state_out,
-                    int16_t* pcm) {
+void orc_dsp_granules(const mp3g_granule* g, const int16_t* coef, size_t n, mp3g_state* st,
+                      int16_t* pcm) {
+  dsp_granules(g, coef, n, st, pcm, NULL);
+}
+
+static void dsp_streams(const mp3g_granule* g, const int16_t* coef, const mp3g_stream* streams,
+                        uint32_t n_streams, const mp3g_state* state_in, mp3g_state* state_out,
+                        int16_t* pcm, float* t_out) {
   ensure_init();
   mp3g_state st;
   for (uint32_t s = 0; s < n_streams; s++) {
     const mp3g_stream* S = &streams[s];
     if (S->flags & MP3G_STREAM_STATE_IN) st = state_in[s];
     else memset(&st, 0, sizeof st);
-    orc_dsp_granules(g + S->first_granule, coef + S->first_granule * 1152, S->n_granules, &st,
-                     pcm + S->first_granule * 1152);
+    dsp_granules(g + S->first_granule, coef + S->first_granule * 1152, S->n_granules, &st,
+                 pcm + S->first_granule * 1152, t_out ? t_out + S->first_granule * 1152 : NULL);
     if (S->flags & MP3G_STREAM_STATE_OUT) state_out[s] = st;
   }
+}
+
+int orc_dsp_streams(const mp3g_granule* g, const int16_t* coef, const mp3g_stream* streams,
+                    uint32_t n_streams, const mp3g_state* state_in, mp3g_state* state_out,
+                    int16_t* pcm) {
+  dsp_streams(g, coef, streams, n_streams, state_in, state_out, pcm, NULL);
+  return 0;
+}
+
+int orc_dsp_streams_f32(const mp3g_granule* g, const int16_t* coef, const mp3g_stream* streams,
+                        uint32_t n_streams, const mp3g_state* state_in, mp3g_state* state_out,
+                        float* t_out) {
+  size_t n = 0;
+  for (uint32_t s = 0; s < n_streams; s++)
+    if (streams[s].first_granule + streams[s].n_granules > n) n = streams[s].first_granule + streams[s].n_granules;
+  int16_t* pcm = (int16_t*)malloc((n ? n : 1) * 1152 * sizeof(int16_t));
+  if (!pcm) return ORC_ERR;
+  dsp_streams(g, coef, streams, n_streams, state_in, state_out, pcm, t_out);
+  free(pcm);
   return 0;
 }
 
@@ -1220,7 +1249,7 @@ int orc_synth_streams(const mp3g_granule* g, const float* is, const mp3g_stream*
     else memset(&st, 0, sizeof st);
     for (uint64_t k = S->first_granule; k < S->first_granule + S->n_granules; k++) {
       const int nch = fh_nch(g[k].header);
-      for (int ch = 0; ch < nch; ch++) dsp_synth(nch, ch, is + k * 1152 + ch * 576, st.vvec[ch], pcm + k * 1152);
+      for (int ch = 0; ch < nch; ch++) dsp_synth(nch, ch, is + k * 1152 + ch * 576, st.vvec[ch], pcm + k * 1152, NULL);
     }
     if (S->flags & MP3G_STREAM_STATE_OUT) state_out[s] = st;
   }

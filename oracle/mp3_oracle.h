@@ -74,6 +74,12 @@ void orc_dsp_granules(const mp3g_granule* g, const int16_t* coef, size_t n, mp3g
 int orc_dsp_streams(const mp3g_granule* g, const int16_t* coef, const mp3g_stream* streams,
                     uint32_t n_streams, const mp3g_state* state_in, mp3g_state* state_out,
                     int16_t* pcm);
+/* Same arguments and state handling; in place of the PCM, t_out [n][576][2]
+ * receives t = sum * 32767.0f, the float32 product the PCM sample truncates,
+ * before the clamp (frame.go:663).  Mono granules write it to both channels. */
+int orc_dsp_streams_f32(const mp3g_granule* g, const int16_t* coef, const mp3g_stream* streams,
+                        uint32_t n_streams, const mp3g_state* state_in, mp3g_state* state_out,
+                        float* t_out);
 /* Stages before the polyphase (requantize .. frequency inversion) only:
  * float32 lines [n][2][576] as subbandSynthesis reads them (test inputs). */
 void orc_hybrid_streams(const mp3g_granule* g, const int16_t* coef, const mp3g_stream* streams,

@@ -60,6 +60,7 @@ def lib():
         L.orc_free.argtypes = [vp]
         L.orc_dsp_granules.argtypes = [vp, vp, sz, vp, vp]
         L.orc_dsp_streams.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp]
+        L.orc_dsp_streams_f32.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp]
         L.orc_dsp_streams_mt.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_int]
         L.orc_hybrid_streams.argtypes = [vp, vp, vp, C.c_uint32, vp, vp]
         L.orc_frontend_granules.argtypes = [vp, vp, sz, vp]
@@ -120,6 +121,24 @@ def dsp_streams(granules, coeffs, streams, state_in=None):
     L.orc_dsp_streams(_ptr(granules), _ptr(coeffs), _ptr(streams), len(streams), _ptr(state_in),
                       _ptr(state_out), _ptr(pcm))
     return pcm, state_out
+
+
+def dsp_streams_float(granules, coeffs, streams, state_in=None):
+    """dsp_streams with the sample before its truncation: (t float32 [n, 576, 2],
+    state_out), t = sum * 32767.0f, the product pcm_sample truncates, unclamped."""
+    L = lib()
+    granules = np.ascontiguousarray(granules, dtype=GRANULE_DTYPE)
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.int16)
+    streams = np.ascontiguousarray(streams, dtype=STREAM_DTYPE)
+    t = np.zeros((len(granules), 576, 2), np.float32)
+    state_out = np.zeros(len(streams), STATE_DTYPE)
+    if state_in is None:
+        state_in = np.zeros(len(streams), STATE_DTYPE)
+    st = L.orc_dsp_streams_f32(_ptr(granules), _ptr(coeffs), _ptr(streams), len(streams), _ptr(state_in),
+                               _ptr(state_out), _ptr(t))
+    if st != ORC_OK:
+        raise MemoryError("orc_dsp_streams_f32")
+    return t, state_out
 
 
 def hybrid_streams(granules, coeffs, streams, state_in=None):

@@ -59,8 +59,17 @@ def _fields(c):
 
 def spec_decode(g, coef, synth_d):
     """float64 decode of one stream of boundary input; returns int16 [n, 576, 2]."""
+    val, _ = spec_decode_float(g, coef, synth_d)
+    return np.clip(np.trunc(val), -32767, 32767).astype(np.int16)
+
+
+def spec_decode_float(g, coef, synth_d):
+    """float64 decode of one stream of boundary input: (val float64 [n, 576, 2],
+    the sample in int16 LSB units before truncation and clamp (a mono granule's
+    in both channels), and the overlap store float64 [2, 32, 18] behind the last
+    granule)."""
     n = len(g)
-    pcm = np.zeros((n, 576, 2), np.int16)
+    out_val = np.zeros((n, 576, 2))
     store = np.zeros((2, 32, 18))
     fifo = np.zeros((2, 15, 64))  # last 15 V blocks, oldest first
     jj = np.arange(16)
@@ -173,10 +182,9 @@ def spec_decode(g, coef, synth_d):
                 bi = 15 + s - jj
                 u = blocks[bi[:, None], i32[None, :] + 32 * (jj[:, None] & 1)]
                 val = (u * synth_d.reshape(16, 32)).sum(0) * 32767.0
-                smp = np.clip(np.trunc(val), -32767, 32767).astype(np.int16)
                 if nch == 1:
-                    pcm[k, 32 * s: 32 * s + 32, 0] = smp
-                    pcm[k, 32 * s: 32 * s + 32, 1] = smp
+                    out_val[k, 32 * s: 32 * s + 32, 0] = val
+                    out_val[k, 32 * s: 32 * s + 32, 1] = val
                 else:
-                    pcm[k, 32 * s: 32 * s + 32, ch] = smp
-    return pcm
+                    out_val[k, 32 * s: 32 * s + 32, ch] = val
+    return out_val, store
