@@ -205,6 +205,20 @@ def lib():
             L.mp3g_loudness_target_energy.restype = C.c_double
             L.mp3g_gain_rows.argtypes = [C.c_int, vp, u32, u32, u32, vp, vp, C.c_double, C.c_float, vp, vp]
             L.mp3g_gain_host.argtypes = [vp, u32, u32, u32, vp, vp, C.c_double, C.c_float, vp]
+        if hasattr(L, "mp3g_true_peak_rows"):
+            L.mp3g_true_peak_coefs.argtypes = [C.POINTER(vp)]
+            L.mp3g_true_peak_tile.argtypes = []
+            L.mp3g_true_peak_tile.restype = u32
+            L.mp3g_true_peak_scratch_bytes.argtypes = [u32, u32, u32]
+            L.mp3g_true_peak_scratch_bytes.restype = u64
+            L.mp3g_true_peak_host.argtypes = [vp, u32, u32, u32, vp, vp]
+            L.mp3g_true_peak_rows.argtypes = [C.c_int, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]
+            L.mp3g_loudness_range_host.argtypes = [vp, vp, u32, u32, u32, vp, vp]
+            L.mp3g_loudness_range_scratch_bytes.argtypes = [vp, u32, u32, u32]
+            L.mp3g_loudness_range_scratch_bytes.restype = u64
+            L.mp3g_loudness_range_rows.argtypes = [vp, u32, u32, u32, vp, vp, u32, vp, vp, vp, vp]
+            L.mp3g_gain_rows_peak.argtypes = [C.c_int, vp, u32, u32, u32, vp, vp, C.c_double, C.c_float, vp, vp, vp]
+            L.mp3g_gain_host_peak.argtypes = [vp, u32, u32, u32, vp, vp, C.c_double, C.c_float, vp, vp]
         L.mp3g_lame_parse.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo)]
         L.mp3g_lame_parse_reader.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo), C.POINTER(C.c_size_t)]
         L.mp3g_lame_total_delay.argtypes = [C.POINTER(_LameInfo)]
@@ -1352,6 +1366,11 @@ LOUDNESS_STATS_DTYPE = np.dtype([("energy", "<f8"), ("lufs", "<f4"), ("peak", "<
                                  ("n_abs", "<u4"), ("n_gated", "<u4"), ("zero", "<u4")])
 assert LOUDNESS_STATS_DTYPE.itemsize == 32
 LOUDNESS_ABS_GATE = 1.1724653045822964e-07
+# one record per row (mp3g_loudness_range)
+LOUDNESS_RANGE_DTYPE = np.dtype([("momentary_max", "<f4"), ("shortterm_max", "<f4"), ("lra", "<f4"),
+                                 ("range_lo", "<f4"), ("range_hi", "<f4"), ("n_short", "<u4"), ("n_range", "<u4"),
+                                 ("zero", "<u4")])
+assert LOUDNESS_RANGE_DTYPE.itemsize == 32
 
 
 def loudness_target_energy(lufs):
@@ -1385,8 +1404,11 @@ class Loudness:
     segments adds what the carried-in state contributes, all in float64 in one
     fixed order, so the device call (execute) equals the host reference (host)
     byte for byte.  shelf and highpass are the two sections as b0 b1 b2 a1 a2;
-    V [H, 4], AH [4, 4] and G [4, 4] the segment tables.  Momentary and
-    short-term loudness, loudness range and true peak are not offered.
+    V [H, 4], AH [4, 4] and G [4, 4] the segment tables.  The largest
+    momentary and short-term loudness and the loudness range (EBU Tech 3342)
+    come from the same pass: range_host, and execute(d_range=); the true peak
+    is mp3g.true_peak.  Surround channel weights and the momentary and
+    short-term time series are not offered.
     device=None (or -1) makes a host-only object."""
 
     def __init__(self, rate, device=None):
@@ -1403,7 +1425,7 @@ class Loudness:
             return np.ctypeslib.as_array(C.cast(q, C.POINTER(C.c_double)), shape=shape)
         self.shelf, self.highpass = view(p[0], (5,)), view(p[1], (5,))
         self.V, self.AH, self.G = view(p[2], (self.H, 4)), view(p[3], (4, 4)), view(p[4], (4, 4))
-        self._scratch = self._keep = None
+        self._scratch = self._range_scratch = self._keep = None
 
     def blocks(self, n):
         """The 400 ms blocks a row of n samples has (mp3g_loudness_blocks)."""
@@ -1428,7 +1450,26 @@ class Loudness:
                                         _ptr(ln) if ln is not None and B else None, _ptr(stats) if B else None))
         return stats
 
-    def execute(self, d_src, lengths=None, rows=None, stream=None, d_stats=None):
+    def range_host(self, x, lengths=None):
+        """The reference on the CPU of the momentary and short-term maxima and
+        the loudness range (mp3g_loudness_range_host): x and lengths as in
+        host().  Returns LOUDNESS_RANGE_DTYPE[B]."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim not in (2, 3):
+            raise ValueError("Loudness.range_host: x is [B, C, T] or [B, T]")
+        B, T = x.shape[0], x.shape[-1]
+        planes = x.shape[1] if x.ndim == 3 else 1
+        ln = None
+        if lengths is not None:
+            ln = np.ascontiguousarray(np.clip(np.asarray(lengths, dtype=np.int64), 0, 2 ** 32 - 1), dtype=np.uint32)
+            if ln.shape != (B,):
+                raise ValueError("Loudness.range_host: one length per row")
+        out = np.zeros(B, LOUDNESS_RANGE_DTYPE)
+        _check(lib().mp3g_loudness_range_host(self._h, _ptr(x) if x.size else None, B, planes, T,
+                                              _ptr(ln) if ln is not None and B else None, _ptr(out) if B else None))
+        return out
+
+    def execute(self, d_src, lengths=None, rows=None, stream=None, d_stats=None, d_range=None):
         """The device call (mp3g_loudness_rows): d_src float32 [B, C, T] (C = 1
         or 2) or [B, T], contiguous on this object's device; lengths: one
         sample count per row (a device tensor or array-like; None: T); rows: the
@@ -1437,7 +1478,10 @@ class Loudness:
         given, else a new zero-filled one): only the records of the measured
         rows are written.  The scratch is a tensor this object keeps and grows.
         Two launches, asynchronous on `stream` (a hipStream_t; None = the
-        current torch stream); read the records with stats()."""
+        current torch stream); read the records with stats().  d_range: a
+        contiguous uint8 device tensor [B, 32] that receives the measured rows'
+        mp3g_loudness_range records (range_stats() reads them), from a third
+        launch behind the two on the same stream (mp3g_loudness_range_rows)."""
         import torch
         if d_src.dtype != torch.float32 or not d_src.is_contiguous() or d_src.dim() not in (2, 3) or not d_src.is_cuda:
             raise ValueError("Loudness.execute: a contiguous float32 device tensor [B, C, T] or [B, T]")
@@ -1449,6 +1493,10 @@ class Loudness:
         if (d_stats.dtype != torch.uint8 or not d_stats.is_contiguous() or not d_stats.is_cuda
                 or tuple(d_stats.shape) != (B, LOUDNESS_STATS_DTYPE.itemsize)):
             raise ValueError("Loudness.execute: d_stats is a contiguous uint8 device tensor [B, 32]")
+        if d_range is not None and (not torch.is_tensor(d_range) or d_range.dtype != torch.uint8
+                                    or not d_range.is_contiguous() or d_range.device != dev
+                                    or tuple(d_range.shape) != (B, LOUDNESS_RANGE_DTYPE.itemsize)):
+            raise ValueError("Loudness.execute: d_range is a contiguous uint8 device tensor [B, 32]")
         d_len = _device_lengths(lengths, B, dev, "Loudness.execute")
         d_rows, n_index = None, 0
         if rows is not None:
@@ -1477,6 +1525,14 @@ class Loudness:
             return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
         _check(lib().mp3g_loudness_rows(self._h, p(d_src), B, planes, T, p(d_len), p(d_rows), n_index,
                                         p(self._scratch), p(d_stats), C.c_void_p(stream) if stream else None))
+        if d_range is not None and B:
+            need = int(lib().mp3g_loudness_range_scratch_bytes(self._h, B, planes, T))
+            if (self._range_scratch is None or self._range_scratch.numel() * 8 < need
+                    or self._range_scratch.device != dev):
+                self._range_scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+            _check(lib().mp3g_loudness_range_rows(self._h, B, planes, T, p(d_len), p(d_rows), n_index,
+                                                  p(self._scratch), p(self._range_scratch), p(d_range),
+                                                  C.c_void_p(stream) if stream else None))
         return d_stats
 
     @staticmethod
@@ -1485,10 +1541,16 @@ class Loudness:
         (synchronises with the device)."""
         return t.cpu().numpy().reshape(-1).view(LOUDNESS_STATS_DTYPE).copy()
 
+    @staticmethod
+    def range_stats(t):
+        """The records execute() left in d_range as a numpy
+        LOUDNESS_RANGE_DTYPE array (synchronises with the device)."""
+        return t.cpu().numpy().reshape(-1).view(LOUDNESS_RANGE_DTYPE).copy()
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self.shelf = self.highpass = self.V = self.AH = self.G = None
-            self._scratch = self._keep = None
+            self._scratch = self._range_scratch = self._keep = None
             lib().mp3g_loudness_free(self._h)
             self._h = C.c_void_p()
 
@@ -1499,12 +1561,13 @@ class Loudness:
             pass
 
 
-def loudness_gain_host(x, stats, target_lufs, peak_ceiling=None, lengths=None):
+def loudness_gain_host(x, stats, target_lufs, peak_ceiling=None, lengths=None, peaks=None):
     """The reference on the CPU (mp3g_gain_host): (y, gains) with y a copy of
     the float32 array x [B, C, T] or [B, T] whose row b is multiplied over its
     first min(lengths[b], T) samples by gains[b] = float32(sqrt(target energy /
     stats[b].energy)), capped at peak_ceiling / stats[b].peak when a ceiling is
-    given; a row of energy 0 is copied and has gain 1."""
+    given; a row of energy 0 is copied and has gain 1.  peaks: float32 [B] that
+    takes the place of stats[b].peak (a true peak, say; mp3g_gain_host_peak)."""
     y = np.array(x, dtype=np.float32, order="C", copy=True)
     if y.ndim not in (2, 3):
         raise ValueError("loudness_gain_host: x is [B, C, T] or [B, T]")
@@ -1519,21 +1582,30 @@ def loudness_gain_host(x, stats, target_lufs, peak_ceiling=None, lengths=None):
         if ln.shape != (B,):
             raise ValueError("loudness_gain_host: one length per row")
     gains = np.ones(B, np.float32)
-    _check(lib().mp3g_gain_host(_ptr(y) if y.size else None, B, planes, T, _ptr(ln) if ln is not None and B else None,
-                                _ptr(stats) if B else None, loudness_target_energy(target_lufs),
-                                0.0 if peak_ceiling is None else float(peak_ceiling), _ptr(gains) if B else None))
+    args = (_ptr(y) if y.size else None, B, planes, T, _ptr(ln) if ln is not None and B else None,
+            _ptr(stats) if B else None, loudness_target_energy(target_lufs),
+            0.0 if peak_ceiling is None else float(peak_ceiling), _ptr(gains) if B else None)
+    if peaks is None:
+        _check(lib().mp3g_gain_host(*args))
+    else:
+        peaks = np.ascontiguousarray(peaks, dtype=np.float32)
+        if peaks.shape != (B,):
+            raise ValueError("loudness_gain_host: one peak per row")
+        _check(lib().mp3g_gain_host_peak(*args, _ptr(peaks) if B else None))
     return y, gains
 
 
-def loudness_gain(d_x, d_stats, target_lufs, peak_ceiling=None, lengths=None, stream=None):
+def loudness_gain(d_x, d_stats, target_lufs, peak_ceiling=None, lengths=None, stream=None, d_peak=None):
     """The device call (mp3g_gain_rows): multiplies the contiguous float32
     device tensor d_x [B, C, T] or [B, T] in place, row b over its first
     min(lengths[b], T) samples, by the gain that brings the loudness d_stats
     (Loudness.execute's records) reports to target_lufs, capped so that the
     sample peak stays at or below peak_ceiling when one is given -- as
     loudness_gain_host states it and bit for bit.  One launch, asynchronous on
-    `stream` (a hipStream_t; None = the current torch stream).  Returns the
-    gains, a float32 device tensor [B]."""
+    `stream` (a hipStream_t; None = the current torch stream).  d_peak: a
+    contiguous float32 device tensor [B] that takes the place of the records'
+    sample peak (mp3g.true_peak's result, say; mp3g_gain_rows_peak).  Returns
+    the gains, a float32 device tensor [B]."""
     import torch
     if (not torch.is_tensor(d_x) or d_x.dtype != torch.float32 or not d_x.is_contiguous() or not d_x.is_cuda
             or d_x.dim() not in (2, 3)):
@@ -1543,21 +1615,122 @@ def loudness_gain(d_x, d_stats, target_lufs, peak_ceiling=None, lengths=None, st
     if (not torch.is_tensor(d_stats) or d_stats.dtype != torch.uint8 or not d_stats.is_contiguous()
             or d_stats.device != d_x.device or tuple(d_stats.shape) != (B, LOUDNESS_STATS_DTYPE.itemsize)):
         raise ValueError("loudness_gain: d_stats is a contiguous uint8 tensor [B, 32] on d_x's device")
+    if d_peak is not None and (not torch.is_tensor(d_peak) or d_peak.dtype != torch.float32
+                               or not d_peak.is_contiguous() or d_peak.device != d_x.device
+                               or tuple(d_peak.shape) != (B,)):
+        raise ValueError("loudness_gain: d_peak is a contiguous float32 tensor [B] on d_x's device")
     d_len = _device_lengths(lengths, B, d_x.device, "loudness_gain")
     gains = torch.empty(B, dtype=torch.float32, device=d_x.device)  # (every row's gain is written)
     if stream is None:
         stream = torch.cuda.current_stream(d_x.device).cuda_stream
-    _check(lib().mp3g_gain_rows(d_x.device.index or 0, C.c_void_p(d_x.data_ptr()) if d_x.numel() else None, B, planes,
-                                T, C.c_void_p(d_len.data_ptr()) if d_len is not None and B else None,
-                                C.c_void_p(d_stats.data_ptr()) if B else None, loudness_target_energy(target_lufs),
-                                0.0 if peak_ceiling is None else float(peak_ceiling),
-                                C.c_void_p(gains.data_ptr()) if B else None, C.c_void_p(stream) if stream else None))
+    args = (d_x.device.index or 0, C.c_void_p(d_x.data_ptr()) if d_x.numel() else None, B, planes,
+            T, C.c_void_p(d_len.data_ptr()) if d_len is not None and B else None,
+            C.c_void_p(d_stats.data_ptr()) if B else None, loudness_target_energy(target_lufs),
+            0.0 if peak_ceiling is None else float(peak_ceiling),
+            C.c_void_p(gains.data_ptr()) if B else None, C.c_void_p(stream) if stream else None)
+    if d_peak is None:
+        _check(lib().mp3g_gain_rows(*args))
+    else:
+        _check(lib().mp3g_gain_rows_peak(*args, C.c_void_p(d_peak.data_ptr()) if B else None))
     return gains
+
+
+# ---- true peak of decoded rows (include/mp3g.h) ---------------------------------------
+def true_peak_coefs():
+    """The interpolator's coefficients, float32 [3, 12]: phases 1..3, delays
+    0..11 (mp3g_true_peak_coefs)."""
+    q = C.c_void_p()
+    _check(lib().mp3g_true_peak_coefs(C.byref(q)))
+    return np.ctypeslib.as_array(C.cast(q, C.POINTER(C.c_float)), shape=(3, 12)).copy()
+
+
+def true_peak_tile():
+    """The samples of a plane one workgroup of the true-peak kernel takes."""
+    return int(lib().mp3g_true_peak_tile())
+
+
+def true_peak_host(x, lengths=None):
+    """The reference on the CPU (mp3g_true_peak_host): the peak of the 4x
+    oversampled signal (libebur128's 49-tap interpolator) of every row of the
+    float32 array x [B, C, T] (C = 1 or 2) or [B, T], over its first
+    min(lengths[b], T) samples.  Returns float32 [B]; 20 log10 of it is dBTP."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim not in (2, 3):
+        raise ValueError("true_peak_host: x is [B, C, T] or [B, T]")
+    B, T = x.shape[0], x.shape[-1]
+    planes = x.shape[1] if x.ndim == 3 else 1
+    ln = None
+    if lengths is not None:
+        ln = np.ascontiguousarray(np.clip(np.asarray(lengths, dtype=np.int64), 0, 2 ** 32 - 1), dtype=np.uint32)
+        if ln.shape != (B,):
+            raise ValueError("true_peak_host: one length per row")
+    tp = np.zeros(B, np.float32)
+    _check(lib().mp3g_true_peak_host(_ptr(x) if x.size else None, B, planes, T,
+                                     _ptr(ln) if ln is not None and B else None, _ptr(tp) if B else None))
+    return tp
+
+
+_tp_scratch = {}  # per device: the partial maxima of the last call (grown, never shrunk)
+_tp_keep = {}  # per device: the last call's lengths and rows, alive while its launches may run
+
+
+def true_peak(d_x, lengths=None, rows=None, stream=None, d_out=None):
+    """The device call (mp3g_true_peak_rows): the true peak of the rows of the
+    contiguous float32 device tensor d_x [B, C, T] (C = 1 or 2) or [B, T], as
+    true_peak_host states it and bit for bit.  lengths: one sample count per row
+    (a device tensor or array-like; None: T); rows: the rows to measure
+    (array-like or an int32 device tensor; None: all).  Returns a float32
+    device tensor [B] (d_out when given, else a new zero-filled one): only the
+    measured rows' entries are written.  Two launches, asynchronous on `stream`
+    (a hipStream_t; None = the current torch stream); the scratch is a tensor
+    kept per device, so calls on one device must be stream-ordered."""
+    import torch
+    if (not torch.is_tensor(d_x) or d_x.dtype != torch.float32 or not d_x.is_contiguous() or not d_x.is_cuda
+            or d_x.dim() not in (2, 3)):
+        raise ValueError("true_peak: a contiguous float32 device tensor [B, C, T] or [B, T]")
+    B, T = int(d_x.shape[0]), int(d_x.shape[-1])
+    planes = int(d_x.shape[1]) if d_x.dim() == 3 else 1
+    dev = d_x.device
+    if d_out is None:
+        d_out = torch.zeros(B, dtype=torch.float32, device=dev)
+    if (not torch.is_tensor(d_out) or d_out.dtype != torch.float32 or not d_out.is_contiguous()
+            or d_out.device != dev or tuple(d_out.shape) != (B,)):
+        raise ValueError("true_peak: d_out is a contiguous float32 tensor [B] on d_x's device")
+    d_len = _device_lengths(lengths, B, dev, "true_peak")
+    d_rows, n_index = None, 0
+    if rows is not None:
+        if torch.is_tensor(rows) and rows.is_cuda:
+            d_rows = rows.to(torch.int32).contiguous()
+        else:
+            host = np.ascontiguousarray(rows, dtype=np.int64)
+            if host.ndim != 1 or (len(host) and (host.min() < 0 or host.max() >= B)):
+                raise ValueError("true_peak: rows lie in [0, B)")
+            d_rows = torch.from_numpy(host.astype(np.int32)).to(dev)
+        n_index = int(d_rows.numel())
+        if n_index > B:
+            raise ValueError("true_peak: more rows than the batch has")
+        if n_index == 0:
+            return d_out
+    need = int(lib().mp3g_true_peak_scratch_bytes(B, planes, T))
+    if B and T and need == 0:
+        _check(lib().mp3g_true_peak_rows(dev.index or 0, None, B, planes, T, None, None, 0, None, None, None))
+    scratch = _tp_scratch.get(dev)
+    if scratch is None or scratch.numel() * 4 < need:
+        scratch = _tp_scratch[dev] = torch.empty(max(1, (need + 3) // 4), dtype=torch.float32, device=dev)
+    _tp_keep[dev] = (d_len, d_rows)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def p(t):
+        return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    _check(lib().mp3g_true_peak_rows(dev.index or 0, p(d_x), B, planes, T, p(d_len), p(d_rows), n_index, p(scratch),
+                                     p(d_out), C.c_void_p(stream) if stream else None))
+    return d_out
 
 
 def decode_windows_normalized_tensor(datas, starts, n_samples, target_lufs=-23.0, peak_ceiling=None, rate=None,
                                      mode=MODE_EXACT, out_format=OUT_F32_PLANAR, gapless=False, quality="fast",
-                                     n_threads=0, device=0):
+                                     n_threads=0, device=0, peak="sample", extended=False):
     """A windowed decode, its loudness and the gain to target_lufs, all on the
     GPU.  rate=None: decode_windows_tensor, each row measured at its stream's
     own rate (stream_rates; one Loudness and one measurement per distinct
@@ -1568,11 +1741,22 @@ def decode_windows_normalized_tensor(datas, starts, n_samples, target_lufs=-23.0
     file's loudness passes a window that covers the file.  A stream with no
     valid frame is an all-zero row with lufs = -inf and gain 1.
 
+    peak="true": the true peak of every row is measured (mp3g.true_peak: one
+    call, the interpolator does not depend on the rate) and peak_ceiling caps
+    the gain against it instead of the sample peak -- the ceiling of EBU R128
+    and of delivery specifications, in dBTP.  extended=True appends range_stats
+    (LOUDNESS_RANGE_DTYPE[B], numpy: Loudness.range_host of the un-normalised
+    batch byte for byte) and true_peaks (float32[B], numpy: true_peak_host of
+    it bit for bit) to the result; a row no meter measures has -inf maxima,
+    lra 0, counts 0 and true peak 0.
+
     Returns what the underlying call returns -- (batch, lengths, end_status)
     or (batch, lengths, end_status, rates) -- followed by stats
     (LOUDNESS_STATS_DTYPE[B], numpy: Loudness.host of the un-normalised batch
     byte for byte) and gains (float32[B], numpy; ones when only measuring)."""
     import torch
+    if peak not in ("sample", "true"):
+        raise ValueError("decode_windows_normalized_tensor: peak is 'sample' or 'true'")
     B = len(datas)
     if rate is None:
         res = decode_windows_tensor(datas, starts, n_samples, mode=mode, out_format=out_format, gapless=gapless,
@@ -1588,20 +1772,33 @@ def decode_windows_normalized_tensor(datas, starts, n_samples, target_lufs=-23.0
     blank["lufs"] = -np.inf
     d_stats = torch.from_numpy(blank.view(np.uint8).reshape(B, -1).copy()).to(batch.device)
     d_len = torch.from_numpy(np.ascontiguousarray(lengths, dtype=np.int32)).to(batch.device)
+    d_range = d_tp = None
+    if extended:
+        blank_range = np.zeros(B, LOUDNESS_RANGE_DTYPE)
+        for name in ("momentary_max", "shortterm_max", "range_lo", "range_hi"):
+            blank_range[name] = -np.inf
+        d_range = torch.from_numpy(blank_range.view(np.uint8).reshape(B, -1).copy()).to(batch.device)
     meters = {int(f): Loudness(int(f), device=device) for f in set(row_rates.tolist()) if f}
     try:
         for f, m in meters.items():
-            m.execute(batch, lengths=d_len, rows=np.nonzero(row_rates == f)[0], d_stats=d_stats)
+            m.execute(batch, lengths=d_len, rows=np.nonzero(row_rates == f)[0], d_stats=d_stats, d_range=d_range)
+        if (extended or peak == "true") and B:
+            # (a row without a frame has length 0: its true peak is 0)
+            d_tp = true_peak(batch, lengths=d_len)
         gains = None
         if target_lufs is not None and B:
-            gains = loudness_gain(batch, d_stats, target_lufs, peak_ceiling=peak_ceiling, lengths=d_len)
+            gains = loudness_gain(batch, d_stats, target_lufs, peak_ceiling=peak_ceiling, lengths=d_len,
+                                  d_peak=d_tp if peak == "true" else None)
         torch.cuda.current_stream(batch.device).synchronize()
     finally:
         for m in meters.values():
             m.close()
     stats = Loudness.stats(d_stats)
     gains = np.ones(B, np.float32) if gains is None else gains.cpu().numpy()
-    return tuple(res) + (stats, gains)
+    if not extended:
+        return tuple(res) + (stats, gains)
+    true_peaks = np.zeros(B, np.float32) if d_tp is None else d_tp.cpu().numpy()
+    return tuple(res) + (stats, gains, Loudness.range_stats(d_range), true_peaks)
 
 
 # ---- STFT and mel spectrograms of decoded rows (include/mp3g.h) ----------------

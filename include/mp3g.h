@@ -59,7 +59,10 @@ extern "C" {
  *    decoded rows -- mp3g_mfcc_*; per-row mean and variance normalisation --
  *    mp3g_cmvn_rows and mp3g_cmvn_host; BS.1770 integrated loudness of decoded
  *    rows and the gain stage -- mp3g_loudness_*, mp3g_gain_rows and
- *    mp3g_gain_host.) */
+ *    mp3g_gain_host; true peak, momentary and short-term maxima and loudness
+ *    range of decoded rows and the gain against a supplied peak --
+ *    mp3g_true_peak_*, mp3g_loudness_range_*, mp3g_gain_rows_peak and
+ *    mp3g_gain_host_peak.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -909,8 +912,9 @@ int mp3g_cmvn_host(float* feats, uint32_t n_rows, uint32_t n_planes, uint32_t n_
  * loudnorm report as "I") and the sample peak of every row of a batch
  * float [n_rows][n_planes][T], n_planes 1 or 2, and a gain stage that brings the
  * rows to a target.  Both planes have channel weight 1; a mono row is one
- * channel.  NOT offered: momentary and short-term loudness, loudness range,
- * true peak (the 4x oversampled kind), surround channel weights.
+ * channel.  The momentary and short-term maxima, the loudness range and the
+ * true peak are the two sections below.  NOT offered: surround channel weights,
+ * the momentary and short-term loudness as time series.
  *
  * mp3g_loudness_create(device, rate): rate 8000 .. 192000 (outside:
  * MP3G_ERR_UNSUPPORTED; rate <= 0 or a null pointer: MP3G_ERR_INVALID_ARGUMENT;
@@ -994,6 +998,119 @@ int mp3g_gain_rows(int device, float* d_x, uint32_t n_rows, uint32_t n_planes, u
                    void* hip_stream);
 int mp3g_gain_host(float* x, uint32_t n_rows, uint32_t n_planes, uint32_t T, const uint32_t* lengths,
                    const mp3g_loudness_stats* stats, double target_energy, float peak_ceiling, float* gain_out);
+
+/* ---- True peak of decoded rows ---------------------------------------------------
+ * The peak of the 4x oversampled signal (dBTP = 20 log10 of it), what
+ * ebur128_true_peak and ffmpeg's ebur128 peak=true report, of every row of a
+ * batch float [n_rows][n_planes][T], n_planes 1 or 2.  The interpolator is
+ * libebur128's: 49 taps at factor 4, a Hann-windowed sinc designed in float64,
+ *   j = 0..48, m = j - 24
+ *   c[j] = (m == 0 ? 1 : sin(m pi/4) / (m pi/4)) * 0.5 (1 - cos(2 pi j / 48))
+ * taps with |c[j]| <= 1e-6 dropped, phase f = j % 4, delay t = j / 4.  Phase 0 is
+ * the single tap c[24] = 1 at delay 6: the sample itself.  Phases 1..3 have 12
+ * taps each (t = 0..11), every one rounded once to float32
+ * (go-mp3_amd/csrc/truepeak_coefs.inc from tools/gen_truepeak.py);
+ * mp3g_true_peak_coefs gives them as [3][12].  Factor 4 is used at every rate:
+ * MP3's rates end at 48 kHz, where libebur128 uses 4 as well (it takes 2 only
+ * from 96 kHz on).
+ *
+ * The measurement, float32 with explicit fmaf and no other contraction
+ * (go-mp3_amd/csrc/truepeak.h).  len_r = T, or min(lengths[r], T) with lengths.
+ * Per plane and n < len_r, with x[k] = 0 for k < 0, for f = 1, 2, 3:
+ *   y_f[n] = fmaf(c_f[11], x[n-11], ... fmaf(c_f[1], x[n-1], fmaf(c_f[0], x[n], 0)))
+ * (the accumulator starts at 0, t ascends), and
+ *   tp_r = max over planes, n and f of |y_f[n]|, and of |x[n]|,
+ * updated as v > tp ? v : tp from tp = 0.  There is no tail flush: the ringing
+ * after len_r is not evaluated (libebur128 does not evaluate it either).  Samples
+ * at or past len_r and anything before a plane's first sample are never used.
+ * The maximum is exact and order-free, so mp3g_true_peak_rows equals
+ * mp3g_true_peak_host bit for bit.
+ *
+ * mp3g_true_peak_rows: d_src, d_lengths (uint32 [n_rows], may be NULL),
+ * d_row_index (uint32 [n_index] rows to measure, may be NULL: all n_rows; values
+ * >= n_rows are skipped), d_scratch (mp3g_true_peak_scratch_bytes, 4-byte
+ * aligned; may be NULL when that is 0) and d_tp (float [n_rows]) are device
+ * pointers.  Two launches whose shapes depend on no device content, no
+ * allocation, asynchronous on hip_stream and graph-capturable; writes the d_tp
+ * entries of the rows it was given and its scratch, nothing else.
+ * mp3g_true_peak_tile: the samples of a plane one workgroup takes. */
+int mp3g_true_peak_coefs(const float** c /* [3][12], phases 1..3 */);
+uint32_t mp3g_true_peak_tile(void);
+uint64_t mp3g_true_peak_scratch_bytes(uint32_t n_rows, uint32_t n_planes, uint32_t T);
+int mp3g_true_peak_host(const float* x, uint32_t n_rows, uint32_t n_planes, uint32_t T, const uint32_t* lengths,
+                        float* tp);
+int mp3g_true_peak_rows(int device, const float* d_src, uint32_t n_rows, uint32_t n_planes, uint32_t T,
+                        const uint32_t* d_lengths, const uint32_t* d_row_index, uint32_t n_index, void* d_scratch,
+                        float* d_tp, void* hip_stream);
+
+/* ---- Momentary and short-term maxima, loudness range ---------------------------------
+ * The rest of what EBU R128 meters and ffmpeg's loudnorm measure, from numbers
+ * the loudness measure above has already formed: the largest momentary (400 ms)
+ * and short-term (3 s) loudness of a row and its loudness range (EBU Tech 3342).
+ *
+ * The scratch of mp3g_loudness_rows, which this section reads.  With
+ * S1 = T / H + 1 and n_work = n_index with d_row_index, else n_rows, it holds
+ * n_work * n_planes * S1 items of 9 doubles, item ((i * n_planes + p) * S1 + j)
+ * for work row i (row d_row_index[i], or i), plane p, segment j, then one float
+ * per item.  After the call, for j < nseg: double 0 is the scanned segment
+ * energy E^p_j, doubles 1..4 the segment pass's g and doubles 5..8 its send,
+ * except that double 1 of plane 0's item i < n_blocks is the momentary block
+ * energy z_i; the floats are the items' sample peaks (item nseg: the ragged
+ * tail's).
+ *
+ * Everything below is float64 in the operation order of
+ * go-mp3_amd/csrc/loudness_range.h, without contraction; nseg, n_blocks, H and
+ * Ga = MP3G_LOUDNESS_ABS_GATE as above.
+ *   momentary: M = max_i z_i;  momentary_max = M > 0 ?
+ *     -0.691f + 10.0f * mp3g_log10f((float)M) : -inf
+ *   short-term: n_short = nseg >= 30 ? nseg - 29 : 0;
+ *     P^p_k = (((E^p_k + E^p_k+1) + ...) + E^p_k+29);  S_k = (P^0_k [+ P^1_k]) / (30 H)
+ *     -- a 3 s block every segment (100 ms, ffmpeg's step; Tech 3342 asks for 1 s
+ *     or less);  shortterm_max from max_k S_k as momentary_max from M
+ *   range: absolute gate S_k >= Ga, sum_abs and n_abs over k ascending;
+ *     relative gate rel = 0.01 * (sum_abs / n_abs) (-20 LU);  the gated set is
+ *     S_k >= Ga && S_k >= rel, n_range its count;  among the gated values in
+ *     ascending order lo has rank ((n_range - 1) * 10 + 50) / 100 and hi rank
+ *     ((n_range - 1) * 95 + 50) / 100 (integer division: the nearest rank, as
+ *     libebur128 and the Tech 3342 reference take it);  range_lo and range_hi
+ *     are -0.691f + 10.0f * mp3g_log10f((float)v), lra = range_hi - range_lo in
+ *     float32;  n_range == 0: lra = 0, range_lo = range_hi = -inf
+ * The selected values do not depend on how ties are ordered.  One record per
+ * row, mp3g_loudness_range (32 bytes).
+ *
+ * mp3g_loudness_range_host runs mp3g_loudness_host's segment pass, scan and
+ * blocks and then the above.  mp3g_loudness_range_rows reads d_loudness_scratch
+ * -- the scratch EXACTLY as mp3g_loudness_rows left it when called with the same
+ * object and the same n_rows, n_planes, T, d_lengths, d_row_index and n_index
+ * earlier on the same stream -- and writes d_range_scratch
+ * (mp3g_loudness_range_scratch_bytes, 8-byte aligned) and the records of the
+ * rows it was given, nothing else; it equals the host byte for byte.  One launch
+ * whose shape depends on no device content, no allocation, asynchronous on
+ * hip_stream and graph-capturable. */
+typedef struct mp3g_loudness_range {
+  float momentary_max, shortterm_max; /* LUFS; -inf: no block */
+  float lra, range_lo, range_hi;      /* LU, LUFS, LUFS */
+  uint32_t n_short, n_range;          /* short-term blocks; past both gates */
+  uint32_t zero;
+} mp3g_loudness_range;
+int mp3g_loudness_range_host(const mp3g_loudness* ld, const float* x, uint32_t n_rows, uint32_t n_planes, uint32_t T,
+                             const uint32_t* lengths, mp3g_loudness_range* out);
+uint64_t mp3g_loudness_range_scratch_bytes(const mp3g_loudness* ld, uint32_t n_rows, uint32_t n_planes, uint32_t T);
+int mp3g_loudness_range_rows(const mp3g_loudness* ld, uint32_t n_rows, uint32_t n_planes, uint32_t T,
+                             const uint32_t* d_lengths, const uint32_t* d_row_index, uint32_t n_index,
+                             const void* d_loudness_scratch, void* d_range_scratch, mp3g_loudness_range* d_out,
+                             void* hip_stream);
+
+/* The gain stage against a supplied peak: mp3g_gain_rows and mp3g_gain_host with
+ * peak[r] (float [n_rows]; a true peak, say) in place of the records' sample
+ * peak.  With the pointer NULL they are mp3g_gain_rows and mp3g_gain_host, bit
+ * for bit. */
+int mp3g_gain_rows_peak(int device, float* d_x, uint32_t n_rows, uint32_t n_planes, uint32_t T,
+                        const uint32_t* d_lengths, const mp3g_loudness_stats* d_stats, double target_energy,
+                        float peak_ceiling, float* d_gain_out, void* hip_stream, const float* d_peak);
+int mp3g_gain_host_peak(float* x, uint32_t n_rows, uint32_t n_planes, uint32_t T, const uint32_t* lengths,
+                        const mp3g_loudness_stats* stats, double target_energy, float peak_ceiling, float* gain_out,
+                        const float* peak);
 
 /* ---- STFT and mel spectrograms of decoded rows --------------------------------
  * The front ends of music and general audio at its native rate: an STFT by FFT
