@@ -258,6 +258,7 @@ struct __align__(16) WaveSmem {
   uint32_t zone[8][2];
 };
 constexpr uint32_t kZones = 8;
+
 // the plan's zone list holds kZoneListPerChunk zones per chunk (kernels.h): a
 // wave records at most kZones, so the list cannot overflow
 static_assert(kZones <= kZoneListPerChunk, "zone list smaller than a chunk's zones");
@@ -406,6 +407,17 @@ __device__ __forceinline__ void wave_sync() {
 // not an asm string: the compiler's wait-count pass then knows that nothing
 // issued before it is still pending.
 __device__ __forceinline__ void settle_vmem() { __builtin_amdgcn_s_waitcnt(0x0f70); }
+
+// An LDS pointer as a 32-bit address in a VGPR of its own, opaque to the
+// compiler (an empty volatile asm: it stays where it is written, so inside
+// the granule loop it is not hoisted across the back edge): what is read
+// through it is addressed as this register plus an immediate offset.
+using lds_float = __attribute__((address_space(3))) float;
+__device__ __forceinline__ const lds_float* col_base(const float* p) {
+  uint32_t a = (uint32_t)(uintptr_t)(const lds_float*)p;
+  asm volatile("" : "+v"(a));
+  return (const lds_float*)(uintptr_t)a;
+}
 
 // Branch-free selects (v_bfi_b32 / v_cndmask): keeps the compiler from turning
 // a per-lane choice between two cheap values into exec-mask branches.
@@ -1236,17 +1248,27 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     // instructions in both layouts.  A pair inside one region is one read (A:
     // 8-B aligned, a ds_read_b64; B: a ds_read2_b32); the two pairs that
     // straddle regions, A's (18, 19) and B's (15, 16), are two ds_read_b32.
+    // The two column pointers as 32-bit LDS addresses the compiler cannot see
+    // through (col_base), made here, inside the granule, and the layout's
+    // displacement added to each: every slot of a column lies within 136 B of
+    // them, so a read's position is its immediate offset.  (Left to itself
+    // the compiler splits the wave's ring address into a lane term, kept as
+    // the base register, and a constant too large for the 8-bit offsets of a
+    // ds_read2, which it then adds in front of each read.)
     const float* RA = &s.ring[ch][pa][0];
     const float* RB = &s.ring[ch][pb][0];
     const int d = par ? 18 : 0;
-    const float* const RAr[3] = {RA + d, RA, RA - d};
-    const float* const RBr[3] = {RB + d, RB, RB - d};
+    const lds_float* const RAo = col_base(RA);
+    const lds_float* const RBo = col_base(RB);
+    const lds_float* const RAr[3] = {RAo + d, RAo, RAo - d};
+    const lds_float* const RBr[3] = {RBo + d, RBo, RBo - d};
+    using lds_f2 = const __attribute__((address_space(3))) f2;
 #pragma unroll
     for (int p = 0; p < 9; p++) acc2[p] = bcast(0.0f);
 #pragma unroll
     for (int v = -14; v <= 16; v += 2) {
       const int za = kHist + v, zb = kHist + v - 1;
-      const f2 A = rregion(za) == rregion(za + 1) ? *reinterpret_cast<const f2*>(RAr[rregion(za)] + za)
+      const f2 A = rregion(za) == rregion(za + 1) ? *(lds_f2*)(RAr[rregion(za)] + za)
                                                   : (f2){RAr[rregion(za)][za], RAr[rregion(za + 1)][za + 1]};
       const f2 B = {RBr[rregion(zb)][zb], RBr[rregion(zb + 1)][zb + 1]};
 #pragma unroll
@@ -1549,8 +1571,8 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
         // (gained: the band gains of this granule carry the 1/sqrt2 already)
         auto ms_pair = [&](float& u, float& v, auto gained) {
           const auto r = __builtin_amdgcn_permlane32_swap(__float_as_int(u), __float_as_int(v), false, false);
-          const float a = __int_as_float(r[0]), b = __int_as_float(r[1]);
-          f2 pq = (f2){a + b, a - b};
+          // (a + b, a - b) on the swapped pair where it lies: one packed add
+          f2 pq = pk::sum_diff((f2){__int_as_float(r[0]), __int_as_float(r[1])});
           if constexpr (!decltype(gained)::value) pq = pq * bcast(inv_sqrt2);
           const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_int(pq.x), __float_as_int(pq.y), false, false);
           u = __int_as_float(r2[0]);
@@ -1743,13 +1765,16 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     if (need_v && act) {
       // (eight 8-B writes; the pair (o[2], o[3]) straddles the fixed slots and
       // those that move with the layout: two 4-B writes)
-      float* col = &s.ring[ch][k][0];
-      float* const colr[3] = {nullptr, col, col - (par ? 18 : 0)};
+      // (the pointer that moves with the layout through col_base: the slots
+      // from j = 3 on are then its immediate offsets, not a base add per write)
+      lds_float* const col = (lds_float*)&s.ring[ch][k][0];
+      lds_float* const colr[3] = {nullptr, col, const_cast<lds_float*>(col_base(&s.ring[ch][k][0])) - (par ? 18 : 0)};
+      using lds_f2 = __attribute__((address_space(3))) f2;
 #pragma unroll
       for (int j = 0; j < 18; j += 2) {
         const int z = kHist + j;
         if (rregion(z) == rregion(z + 1)) {
-          *reinterpret_cast<f2*>(colr[rregion(z)] + z) = (f2){o[j], o[j + 1]};
+          *(lds_f2*)(colr[rregion(z)] + z) = (f2){o[j], o[j + 1]};
         } else {
           colr[rregion(z)][z] = o[j];
           colr[rregion(z + 1)][z + 1] = o[j + 1];
@@ -1773,7 +1798,9 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       // in place; this one keeps consecutive lanes on consecutive dwords)
       const int slot = lane & 31;
       if (need_v && act && slot < 18) {
-        float* colu = &s.ring[ch][0][0] + cur + slot;  // S[k] / X at colu[kSlots * k]
+        // S[k] / X at colu[kSlots * k] (through col_base: the 32 columns' 4.2 KB
+        // then take one base register fewer for the 8-bit offsets of ds_*2_b32)
+        lds_float* const colu = const_cast<lds_float*>(col_base(&s.ring[ch][0][0] + cur + slot));
         dct32::f2 sp[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) sp[q] = (dct32::f2){colu[kSlots * 2 * q], colu[kSlots * (2 * q + 1)]};
@@ -1837,6 +1864,10 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     stamp(7);
   }
   if constexpr (kStamp) rt[2] = __builtin_amdgcn_s_memrealtime();
+  // the wave's LDS slot again, its number from the wave-uniform chunk index:
+  // taken from `s`, the wave number (of threadIdx.x, a VGPR) is kept for this
+  // rare code across the whole granule loop -- at 128 VGPRs, in scratch
+  WaveSmem& se = wsm[ci - blockIdx.x * kWaves];
 
   // Frame.store / vVec after the chunk's last granule (frame.go:48-49); Pn:
   // the layout the next granule would have used, whose history the last 15 V
@@ -1856,7 +1887,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       const int cc = e >> 10, blk = (e >> 6) & 15, i = e & 63;
       const int z = kHist - 1 - blk;  // (blk < 15: a history slot)
       const float sig = scaled ? dct32::kScale[m_of_v(i)] : 1.0f;
-      so->vvec[cc][64 * blk + i] = blk < 15 ? v_from_x(&s.ring[cc][0][0] + (Pn ? 18 + z : z), i) * sig : 0.0f;
+      so->vvec[cc][64 * blk + i] = blk < 15 ? v_from_x(&se.ring[cc][0][0] + (Pn ? 18 + z : z), i) * sig : 0.0f;
     }
   };
   static_assert(rphys(1, 1) == 19 && rphys(1, 15) == 33 && rphys(0, 15) == 15, "export_state's history positions");
@@ -1889,7 +1920,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     // atomic for all of them
     uint32_t n_pieces = 0;
     for (uint32_t i = 0; i < nz; i++) {
-      const uint32_t zs = __builtin_amdgcn_readfirstlane(s.zone[i][0]), ze = __builtin_amdgcn_readfirstlane(s.zone[i][1]);
+      const uint32_t zs = __builtin_amdgcn_readfirstlane(se.zone[i][0]), ze = __builtin_amdgcn_readfirstlane(se.zone[i][1]);
       n_pieces += (ze - zs + kZonePiece - 1) / kZonePiece;
     }
     uint32_t base = 0;
@@ -1908,8 +1939,8 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
       if (base + p >= zone_cap) break;
       uint32_t zs = 0, ze = 0, l = p;  // the zone of piece p, and p's index in it
       for (uint32_t i = 0; i < nz; i++) {
-        zs = s.zone[i][0];
-        ze = s.zone[i][1];
+        zs = se.zone[i][0];
+        ze = se.zone[i][1];
         const uint32_t np = (ze - zs + kZonePiece - 1) / kZonePiece;
         if (l < np) break;
         l -= np;
@@ -1940,7 +1971,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     if (nz || n_flagged) {
       uint32_t n_out = 0;
       for (uint32_t i = 0; i < nz; i++)
-        n_out += __builtin_amdgcn_readfirstlane(s.zone[i][1]) - __builtin_amdgcn_readfirstlane(s.zone[i][0]);
+        n_out += __builtin_amdgcn_readfirstlane(se.zone[i][1]) - __builtin_amdgcn_readfirstlane(se.zone[i][0]);
       if (lane_fresh() == 0) {
         atomicAdd(hot_count + 0, n_out);
         atomicAdd(hot_count + 1, nz);
@@ -1954,8 +1985,8 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     bool have = false;
     uint32_t n_out = 0, n_run = 0;  // for hot_count (kernels.h kHotCounters)
     for (uint32_t i = 0; i < nz; i++) {
-      const uint32_t zs = __builtin_amdgcn_readfirstlane(s.zone[i][0]);
-      uint32_t ze = __builtin_amdgcn_readfirstlane(s.zone[i][1]);
+      const uint32_t zs = __builtin_amdgcn_readfirstlane(se.zone[i][0]);
+      uint32_t ze = __builtin_amdgcn_readfirstlane(se.zone[i][1]);
       if (have && ze <= done) continue;
       uint32_t gz = done;
       if (!have || zs > done) {  // a fresh zone: replay from its start's replay start
@@ -1965,7 +1996,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
         uint64_t wz;
         int zin[2];
         prologue(cr, gran, &wz, zin, lane_fresh());
-        init_state(s, sin, zin, lane_fresh(), zst);
+        init_state(se, sin, zin, lane_fresh(), zst);
         gz = __builtin_amdgcn_readfirstlane((uint32_t)wz);
         have = true;
       }
@@ -1973,7 +2004,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
         const bool nv = replay_needs_v(gran, gz, zs);
         n_run++;
         n_out += gz >= zs ? 1u : 0u;
-        if (exact_granule(gran, coef, pcm, s, sh, gz, gz >= zs, nv, zst)) {
+        if (exact_granule(gran, coef, pcm, se, sh, gz, gz >= zs, nv, zst)) {
           const uint32_t e = zone_end(gran, gz, end);
           ze = e > ze ? e : ze;
         }

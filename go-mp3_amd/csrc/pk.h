@@ -57,6 +57,18 @@ MP3G_PK f2 sub_mi(f2 a, f2 b) {
 #endif
 }
 
+// (v.x + v.y, v.x - v.y): one instruction on the pair where it lies (both
+// sources the same pair, so the result can take its place)
+MP3G_PK f2 sum_diff(f2 v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  f2 r;
+  asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[1,0]" : "=v"(r) : "v"(v));  // (x + y, -y + x)
+  return r;
+#else
+  return mk(v.x + v.y, v.x - v.y);
+#endif
+}
+
 // t + k (-i) d = (t.x + k d.y, t.y - k d.x); kNeg: t - k (-i) d
 template <bool kNeg>
 MP3G_PK f2 fma_mi(float k, f2 d, f2 t) {
