@@ -76,12 +76,9 @@ def _masked(g):
     return g
 
 
-@pytest.fixture(scope="module")
-def hjob_host(tmp_path_factory):
-    """tests/native/hjob_host.hip: the device job decoder built for the CPU."""
-    out = tmp_path_factory.mktemp("native") / "libhjob_host.so"
-    # MP3G_HJOB_FLAGS: extra -D knobs of a variant build (e.g. -DMP3G_HUFF_ROOT_BITS=10)
-    extra = os.environ.get("MP3G_HJOB_FLAGS", "").split()
+def build_hjob_host(out, extra=()):
+    """tests/native/hjob_host.hip built into the shared library `out`; extra:
+    -D knobs of a variant build (e.g. -DMP3G_HUFF_ROOT_BITS=10)."""
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950",
                            *extra, "-o", str(out), os.path.join(REPO, "tests", "native", "hjob_host.hip"),
                            os.path.join(REPO, "go-mp3_amd", "csrc", "huff_lut.cpp")])
@@ -89,6 +86,14 @@ def hjob_host(tmp_path_factory):
     L.hjob_decode_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.hjob_decode_host_staged.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     return L
+
+
+@pytest.fixture(scope="module")
+def hjob_host(tmp_path_factory):
+    """tests/native/hjob_host.hip: the device job decoder built for the CPU."""
+    # MP3G_HJOB_FLAGS: extra -D knobs of a variant build
+    return build_hjob_host(tmp_path_factory.mktemp("native") / "libhjob_host.so",
+                           os.environ.get("MP3G_HJOB_FLAGS", "").split())
 
 
 def check_against_parse(hjob_host, datas, what):
