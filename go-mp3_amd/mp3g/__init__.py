@@ -189,6 +189,15 @@ def lib():
             L.mp3g_mfcc_execute.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
             L.mp3g_cmvn_rows.argtypes = [C.c_int, vp, u32, u32, u32, u32, u32, vp, u32, vp]
             L.mp3g_cmvn_host.argtypes = [vp, u32, u32, u32, u32, u32, vp, u32]
+        if hasattr(L, "mp3g_sliding_cmn_rows"):
+            f32 = C.c_float
+            L.mp3g_sliding_cmn_rows.argtypes = [C.c_int, vp, vp, u32, u32, u32, u32, u32, vp, u32, u32, u32, vp]
+            L.mp3g_sliding_cmn_host.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, u32, u32, u32]
+            L.mp3g_vad_energy_rows.argtypes = [C.c_int, vp, u32, u32, u32, u32, u32, u32, vp, f32, f32, f32, u32, vp,
+                                               vp, vp]
+            L.mp3g_vad_energy_host.argtypes = [vp, u32, u32, u32, u32, u32, u32, vp, f32, f32, f32, u32, vp, vp]
+            L.mp3g_select_frames_rows.argtypes = [C.c_int, vp, u32, u32, u32, u32, u32, vp, vp, vp, u32, u32, vp, vp]
+            L.mp3g_select_frames_host.argtypes = [vp, u32, u32, u32, u32, u32, vp, vp, vp, u32, u32, vp]
         if hasattr(L, "mp3g_loudness_create"):
             dp = C.POINTER(vp)
             L.mp3g_loudness_create.argtypes = [C.c_int, C.c_int, dp]
@@ -1314,12 +1323,199 @@ def cmvn(feats, frame_lengths, norm_vars=False, stream=None, n_cols=None):
 _cmvn_rows = cmvn  # (decode_windows_mfcc_tensor has a parameter of that name)
 
 
+# ---- sliding-window CMN, energy VAD and voiced-frame selection (include/mp3g.h) --
+SCMN_CENTER = 1
+SCMN_NORM_VARS = 2
+SLIDING_CMVN_MODES = {"sliding": False, "sliding_var": True}
+VAD_OPTIONS = ("energy_threshold", "energy_mean_scale", "proportion_threshold", "frames_context")
+
+
+def _host_feats(name, feats, frame_lengths, n_cols):
+    """(x float32 C-order [B, (C,) F, S], B, planes, lengths uint32 [B], cols) of a host call."""
+    x = np.ascontiguousarray(feats, dtype=np.float32)
+    if x.ndim not in (3, 4):
+        raise ValueError(name + ": feats is [B, F, S] or [B, C, F, S]")
+    B, planes = x.shape[0], (x.shape[1] if x.ndim == 4 else 1)
+    lengths = np.ascontiguousarray(np.minimum(np.asarray(frame_lengths, dtype=np.int64), 2 ** 32 - 1), dtype=np.uint32)
+    if lengths.shape != (B,):
+        raise ValueError(name + ": one frame length per row")
+    return x, B, planes, lengths, (x.shape[-1] if n_cols is None else int(n_cols))
+
+
+def _device_feats(name, feats, frame_lengths, n_cols):
+    """(B, planes, lengths int32 device tensor [B], cols) of a device call on feats."""
+    import torch
+    if (not torch.is_tensor(feats) or feats.dtype != torch.float32 or not feats.is_contiguous() or not feats.is_cuda
+            or feats.dim() not in (3, 4)):
+        raise ValueError(name + ": a contiguous float32 device tensor [B, F, S] or [B, C, F, S]")
+    B, planes = int(feats.shape[0]), (int(feats.shape[1]) if feats.dim() == 4 else 1)
+    if torch.is_tensor(frame_lengths) and frame_lengths.is_cuda:
+        lengths = frame_lengths.to(torch.int32).contiguous()
+    else:
+        host = np.ascontiguousarray(np.minimum(np.asarray(frame_lengths, dtype=np.int64), 2 ** 31 - 1), dtype=np.int32)
+        lengths = torch.from_numpy(host).to(feats.device)
+    if tuple(lengths.shape) != (B,):
+        raise ValueError(name + ": one frame length per row")
+    return B, planes, lengths, (int(feats.shape[-1]) if n_cols is None else int(n_cols))
+
+
+def _dptr(t):
+    return C.c_void_p(t.data_ptr()) if t.numel() else None
+
+
+def _stream_of(t, stream):
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream(t.device).cuda_stream
+    return C.c_void_p(stream) if stream else None
+
+
+def sliding_cmn_host(feats, frame_lengths, cmn_window=600, min_window=100, center=False, norm_vars=False, n_cols=None):
+    """The reference on the CPU (mp3g_sliding_cmn_host; Kaldi's
+    apply-cmvn-sliding, torchaudio.functional.sliding_window_cmn): a copy of the
+    float32 array feats [B, F, S] or [B, C, F, S] in which every column below
+    n_cols of each row's first min(frame_lengths[b], F) frames has the mean of
+    its window of up to cmn_window frames subtracted (centred on the frame, or
+    the frames before it and at least min_window of them at a row's start) and,
+    with norm_vars, is divided by the window's standard deviation (the variance
+    floored at 1e-10).  The sums are float64, in the blocked order of
+    include/mp3g.h."""
+    x, B, planes, lengths, cols = _host_feats("sliding_cmn_host", feats, frame_lengths, n_cols)
+    out = x.copy()
+    flags = (SCMN_CENTER if center else 0) | (SCMN_NORM_VARS if norm_vars else 0)
+    _check(lib().mp3g_sliding_cmn_host(_ptr(x) if x.size else None, _ptr(out) if out.size else None, B, planes,
+                                       x.shape[-2], x.shape[-1], cols, _ptr(lengths) if B else None, int(cmn_window),
+                                       int(min_window), flags))
+    return out
+
+
+def sliding_cmn(feats, frame_lengths, cmn_window=600, min_window=100, center=False, norm_vars=False, out=None,
+                n_cols=None, stream=None):
+    """The device call (mp3g_sliding_cmn_rows): as sliding_cmn_host states it
+    and bit for bit, from the contiguous float32 device tensor feats [B, F, S]
+    or [B, C, F, S] into `out` (another tensor like it; made here when None, and
+    then columns from n_cols on are copies too).  frame_lengths as for cmvn.  One
+    launch, asynchronous on `stream` (a hipStream_t; None = the current torch
+    stream).  Returns out."""
+    import torch
+    B, planes, lengths, cols = _device_feats("sliding_cmn", feats, frame_lengths, n_cols)
+    if out is None:
+        out = feats.clone() if cols < int(feats.shape[-1]) else torch.empty_like(feats)
+    if (not torch.is_tensor(out) or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != feats.shape
+            or out.device != feats.device):
+        raise ValueError("sliding_cmn: out is a contiguous float32 tensor like feats")
+    flags = (SCMN_CENTER if center else 0) | (SCMN_NORM_VARS if norm_vars else 0)
+    _check(lib().mp3g_sliding_cmn_rows(feats.device.index or 0, _dptr(feats), _dptr(out), B, planes,
+                                       int(feats.shape[-2]), int(feats.shape[-1]), cols, _dptr(lengths),
+                                       int(cmn_window), int(min_window), flags, _stream_of(feats, stream)))
+    return out
+
+
+def vad_energy_host(feats, frame_lengths, energy_threshold=5.0, energy_mean_scale=0.5, proportion_threshold=0.6,
+                    frames_context=0, col=0, n_cols=None):
+    """The reference on the CPU (mp3g_vad_energy_host; Kaldi's
+    compute-vad-energy): (voiced uint8 [B, (C,) F], counts int32 [B, (C)]).
+    Frame t of a row's first min(frame_lengths[b], F) is voiced when, of the
+    frames within frames_context of it, at least proportion_threshold have
+    feats[..., col] above energy_threshold + energy_mean_scale * (the column's
+    mean over the row); the comparison of the proportion is float32, as
+    Kaldi's.  Frames past the length are 0."""
+    x, B, planes, lengths, cols = _host_feats("vad_energy_host", feats, frame_lengths, n_cols)
+    voiced = np.zeros(x.shape[:-1], np.uint8)
+    counts = np.zeros(x.shape[:-2], np.uint32)
+    _check(lib().mp3g_vad_energy_host(_ptr(x) if x.size else None, B, planes, x.shape[-2], x.shape[-1], cols, int(col),
+                                      _ptr(lengths) if B else None, float(energy_threshold), float(energy_mean_scale),
+                                      float(proportion_threshold), int(frames_context),
+                                      _ptr(voiced) if voiced.size else None, _ptr(counts) if counts.size else None))
+    return voiced, counts.astype(np.int32)
+
+
+def vad_energy(feats, frame_lengths, energy_threshold=5.0, energy_mean_scale=0.5, proportion_threshold=0.6,
+               frames_context=0, col=0, n_cols=None, out=None, stream=None):
+    """The device call (mp3g_vad_energy_rows): as vad_energy_host states it and
+    bit for bit, on the contiguous float32 device tensor feats [B, F, S] or
+    [B, C, F, S].  Returns device tensors (voiced uint8 [B, (C,) F], counts
+    int32 [B, (C)]): `out`, a pair of such contiguous tensors, when given.  One
+    launch, asynchronous on `stream`."""
+    import torch
+    B, planes, lengths, cols = _device_feats("vad_energy", feats, frame_lengths, n_cols)
+    if out is None:
+        out = (torch.empty(tuple(feats.shape[:-1]), dtype=torch.uint8, device=feats.device),
+               torch.empty(tuple(feats.shape[:-2]), dtype=torch.int32, device=feats.device))
+    voiced, counts = out
+    if (voiced.dtype != torch.uint8 or counts.dtype != torch.int32 or not voiced.is_contiguous()
+            or not counts.is_contiguous() or voiced.shape != feats.shape[:-1] or counts.shape != feats.shape[:-2]
+            or voiced.device != feats.device or counts.device != feats.device):
+        raise ValueError("vad_energy: out is (uint8 [B, (C,) F], int32 [B, (C)]), contiguous on feats' device")
+    _check(lib().mp3g_vad_energy_rows(feats.device.index or 0, _dptr(feats), B, planes, int(feats.shape[-2]),
+                                      int(feats.shape[-1]), cols, int(col), _dptr(lengths), float(energy_threshold),
+                                      float(energy_mean_scale), float(proportion_threshold), int(frames_context),
+                                      _dptr(voiced), _dptr(counts), _stream_of(feats, stream)))
+    return voiced, counts
+
+
+def select_frames_host(feats, voiced, frame_lengths, n_frames_out=None, n_cols=None, out=None):
+    """The reference on the CPU (mp3g_select_frames_host; Kaldi's
+    select-voiced-frames, kept dense): (out float32 [B, (C,) n_frames_out, S],
+    lengths_out int32 [B, (C)]).  out[b, j] is the j-th frame of feats[b] below
+    the row's length with voiced != 0, columns below n_cols; the frames after
+    the last one are +0; lengths_out = min(count, n_frames_out).  n_frames_out:
+    F by default.  `out`, when given, is an array [B, (C,) n_frames_out, S_out]
+    whose other words are kept (a copy is returned)."""
+    x, B, planes, lengths, cols = _host_feats("select_frames_host", feats, frame_lengths, n_cols)
+    v = np.ascontiguousarray(voiced, dtype=np.uint8)
+    if v.shape != x.shape[:-1]:
+        raise ValueError("select_frames_host: voiced is [B, (C,) F]")
+    if out is None:
+        Fo = x.shape[-2] if n_frames_out is None else int(n_frames_out)
+        y = np.zeros(x.shape[:-2] + (Fo, x.shape[-1]), np.float32)
+    else:
+        y = np.array(out, dtype=np.float32, order="C", copy=True)
+        if y.ndim != x.ndim or y.shape[:-2] != x.shape[:-2]:
+            raise ValueError("select_frames_host: out is [B, (C,) n_frames_out, S_out]")
+    m = np.zeros(x.shape[:-2], np.uint32)
+    _check(lib().mp3g_select_frames_host(_ptr(x) if x.size else None, B, planes, x.shape[-2], x.shape[-1], cols,
+                                         _ptr(v) if v.size else None, _ptr(lengths) if B else None,
+                                         _ptr(y) if y.size else None, y.shape[-2], y.shape[-1],
+                                         _ptr(m) if m.size else None))
+    return y, m.astype(np.int32)
+
+
+def select_frames(feats, voiced, frame_lengths, n_frames_out=None, n_cols=None, out=None, stream=None):
+    """The device call (mp3g_select_frames_rows): as select_frames_host states
+    it and bit for bit.  feats as for vad_energy, voiced a uint8 device tensor
+    [B, (C,) F] (vad_energy's).  out: a contiguous float32 device tensor [B,
+    (C,) n_frames_out, S_out] (made here when None: n_frames_out frames, F by
+    default, of S columns).  No frame count is read back: the output keeps its
+    static shape.  Returns (out, lengths_out int32 [B, (C)]).  One launch,
+    asynchronous on `stream`."""
+    import torch
+    B, planes, lengths, cols = _device_feats("select_frames", feats, frame_lengths, n_cols)
+    if (not torch.is_tensor(voiced) or voiced.dtype != torch.uint8 or not voiced.is_contiguous()
+            or voiced.device != feats.device or voiced.shape != feats.shape[:-1]):
+        raise ValueError("select_frames: voiced is a contiguous uint8 device tensor [B, (C,) F]")
+    if out is None:
+        Fo = int(feats.shape[-2]) if n_frames_out is None else int(n_frames_out)
+        out = torch.empty(tuple(feats.shape[:-2]) + (Fo, int(feats.shape[-1])), dtype=torch.float32,
+                          device=feats.device)
+        if cols < int(feats.shape[-1]):
+            out.zero_()
+    if (not torch.is_tensor(out) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != feats.device
+            or out.dim() != feats.dim() or out.shape[:-2] != feats.shape[:-2]):
+        raise ValueError("select_frames: out is a contiguous float32 device tensor [B, (C,) n_frames_out, S_out]")
+    m = torch.empty(tuple(feats.shape[:-2]), dtype=torch.int32, device=feats.device)
+    _check(lib().mp3g_select_frames_rows(feats.device.index or 0, _dptr(feats), B, planes, int(feats.shape[-2]),
+                                         int(feats.shape[-1]), cols, _dptr(voiced), _dptr(lengths), _dptr(out),
+                                         int(out.shape[-2]), int(out.shape[-1]), _dptr(m), _stream_of(feats, stream)))
+    return out, m
+
+
 def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_length_ms=25.0, frame_shift_ms=10.0,
                                n_mels=23, n_ceps=13, cepstral_lifter=22.0, use_energy=True, raw_energy=True,
                                energy_floor=0.0, low_freq=20.0, high_freq=0.0, preemphasis=0.97, remove_dc=True,
                                window="povey", snip_edges=True, scale=32768.0, cmvn=None, n_frames=None,
                                mode=MODE_EXACT, out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0,
-                               device=0):
+                               device=0, cmn_window=300, min_cmn_window=100, center=True, vad=None):
     """decode_windows_resampled_tensor, MFCC.execute and, with cmvn = "mean"
     or "mean_var", the per-row normalisation over each stream's own frames, all
     on the current torch stream: Kaldi's MFCC features of each stream's window
@@ -1331,10 +1527,25 @@ def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_lengt
     equal to MFCC.host (then cmvn_host) on the rows of
     decode_windows_resampled_tensor bit for bit; frame_lengths int64[B] as
     decode_windows_fbank_tensor counts them.  Frames past a stream's
-    frame_lengths are not normalised."""
+    frame_lengths are not normalised.
+
+    The speaker recipes' front end: cmvn = "sliding" or "sliding_var" is the
+    sliding-window normalisation instead (sliding_cmn with cmn_window,
+    min_cmn_window and center), and vad, a dict of vad_energy's options
+    (energy_threshold, energy_mean_scale, proportion_threshold,
+    frames_context), selects the voiced frames: the decision is taken on the raw
+    features' coefficient 0 (use_energy is required), the normalisation of
+    whichever kind runs over all of a stream's frames, the selection comes last
+    (select_frames; the frames after the voiced ones are zeros).  frame_lengths
+    are then the voiced counts, int64 [B] or, planar, [B, 2]."""
     import torch
-    if cmvn not in CMVN_MODES:
-        raise Mp3gError(1, "decode_windows_mfcc_tensor: cmvn is None, 'mean' or 'mean_var'")
+    if cmvn not in CMVN_MODES and cmvn not in SLIDING_CMVN_MODES:
+        raise Mp3gError(1, "decode_windows_mfcc_tensor: cmvn is None, 'mean', 'mean_var', 'sliding' or 'sliding_var'")
+    if vad is not None:
+        if not isinstance(vad, dict) or set(vad) - set(VAD_OPTIONS):
+            raise Mp3gError(1, "decode_windows_mfcc_tensor: vad is None or a dict of " + ", ".join(VAD_OPTIONS))
+        if not use_energy:
+            raise Mp3gError(1, "decode_windows_mfcc_tensor: vad needs use_energy (coefficient 0 is the log energy)")
     mf = MFCC(rate, frame_length_ms, frame_shift_ms, n_mels, n_ceps, cepstral_lifter, use_energy, raw_energy,
               energy_floor, low_freq, high_freq, preemphasis, remove_dc, window, snip_edges, scale, device=device)
     try:
@@ -1352,8 +1563,15 @@ def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_lengt
             flen = np.clip((lengths - mf.N) // mf.hop + 1, 0, F)
         else:
             flen = np.minimum(F, (lengths + mf.hop // 2) // mf.hop)
-        if CMVN_MODES[cmvn] is not None:
+        if vad is not None:  # (on the raw features)
+            voiced, _ = vad_energy(feats, flen, **vad)
+        if cmvn in SLIDING_CMVN_MODES:
+            feats = sliding_cmn(feats, flen, cmn_window, min_cmn_window, center, SLIDING_CMVN_MODES[cmvn])
+        elif CMVN_MODES[cmvn] is not None:
             _cmvn_rows(feats, flen, norm_vars=CMVN_MODES[cmvn])
+        if vad is not None:
+            feats, counts = select_frames(feats, voiced, flen)
+            flen = counts.cpu().numpy().astype(np.int64)  # (the copy waits for the stream)
         torch.cuda.current_stream(feats.device).synchronize()
     finally:
         mf.close()

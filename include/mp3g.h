@@ -62,7 +62,9 @@ extern "C" {
  *    mp3g_gain_host; true peak, momentary and short-term maxima and loudness
  *    range of decoded rows and the gain against a supplied peak --
  *    mp3g_true_peak_*, mp3g_loudness_range_*, mp3g_gain_rows_peak and
- *    mp3g_gain_host_peak.) */
+ *    mp3g_gain_host_peak; sliding-window CMN, energy VAD and voiced-frame
+ *    selection of feature tensors -- mp3g_sliding_cmn_*, mp3g_vad_energy_* and
+ *    mp3g_select_frames_*.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -906,6 +908,92 @@ int mp3g_cmvn_rows(int device, float* d_feats, uint32_t n_rows, uint32_t n_plane
                    uint32_t stride, uint32_t n_cols, const uint32_t* d_lengths, uint32_t flags, void* hip_stream);
 int mp3g_cmvn_host(float* feats, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames, uint32_t stride,
                    uint32_t n_cols, const uint32_t* lengths, uint32_t flags);
+
+/* ---- Sliding-window CMN, energy VAD and voiced-frame selection -----------------
+ * The three steps Kaldi's speaker recipes (voxceleb, sre16, callhome) run between
+ * compute-mfcc-feats and the network -- apply-cmvn-sliding (what
+ * torchaudio.functional.sliding_window_cmn computes), compute-vad-energy and
+ * select-voiced-frames -- on a time-major feature tensor float [n_rows][n_planes]
+ * [n_frames][stride] of which n_cols <= stride columns are live: the output of
+ * mp3g_fbank_execute or mp3g_mfcc_execute.  lengths: uint32 [n_rows], one frame
+ * count per row as for mp3g_cmvn_rows; below, n = min(lengths[r], n_frames).
+ * Every device call (*_rows: device pointers throughout) equals its host call
+ * bit for bit, is one launch whose shape depends on no buffer's contents,
+ * asynchronous on hip_stream, and allocates nothing.
+ *
+ * Sliding-window CMN.  Out of place (a frame reads neighbours up to a window
+ * away): out has in's shape and must not overlap it.  cmn_window = W >= 1,
+ * min_window >= 1, flags MP3G_SCMN_CENTER and MP3G_SCMN_NORM_VARS.  The window
+ * [s, e) of frame t < n, in signed integers:
+ *   centred: s = t - W / 2 (integer division), e = s + W
+ *   otherwise: s = t - W, e = t + 1
+ *   if s < 0: e -= s, s = 0
+ *   if not centred and e > t: e = max(t + 1, min_window)
+ *   if e > n: s -= e - n, e = n, s = max(s, 0)
+ * so 0 <= s <= t < e <= n, and s and e never decrease in t (they grow by at most
+ * one per frame).  The sums, per plane and column, in ONE written-down order:
+ * frames are cut into blocks of K = 32;
+ *   b[j]  = the float64 sum of (double)x[f] over block j, f ascending from +0.0
+ *   Bp[j] = the float64 sum of b[0..j), ascending from +0.0
+ *   P[f]  = Bp[f / K] + (block f / K's partial sum up to but excluding f,
+ *           ascending from +0.0),  0 <= f <= n
+ *   P2 the same over the exact products (double)x * (double)x
+ *   mean = (P[e] - P[s]) / (e - s);  y[t] = (float)((double)x[t] - mean)
+ *   with NORM_VARS: var = (P2[e] - P2[s]) / (e - s) - mean * mean (the product
+ *   rounded first);  scale = 1.0f / sqrtf(fmaxf((float)var, 1e-10f)) -- Kaldi's
+ *   floor for this tool, not mp3g_cmvn_rows' 1e-20;  y[t] *= scale, one rounded
+ *   float32 product.  A window of one frame gives +0.
+ * Frames f >= n (a row with n = 0: all of them) have their n_cols live columns
+ * copied from in; words at columns >= n_cols are never written.  stride < n_cols,
+ * an unknown flag, W = 0, min_window = 0, out overlapping in or a null pointer
+ * with work to do is MP3G_ERR_INVALID_ARGUMENT before any device call; no rows,
+ * planes, frames or columns is MP3G_OK with nothing done.  The device call keeps
+ * a row's block sums in LDS: n_frames above 20,479 with NORM_VARS, 40,959
+ * without, is MP3G_ERR_UNSUPPORTED.
+ *
+ * Energy VAD on column col < n_cols (the log energy: coefficient 0 of an MFCC
+ * made with MP3G_MFCC_USE_ENERGY), per plane:
+ *   thr = energy_threshold exactly when energy_mean_scale == 0 (the column is
+ *   then not summed); otherwise thr = (float)((double)energy_threshold +
+ *   (double)energy_mean_scale * (P[n] / (double)n)), P the blocked sum above
+ *   for t < n: den = the number of t2 in [t - c, t + c] within [0, n), c =
+ *   frames_context; num = how many of those have x[t2] > thr (a float32
+ *   comparison);  voiced[t] = (float)num >= (float)den * proportion_threshold,
+ *   the product in float32, rounded once (Kaldi's BaseFloat)
+ * voiced: uint8 [n_rows][n_planes][n_frames], frames t >= n written 0; counts:
+ * uint32 [n_rows][n_planes], the ones of each plane (n = 0: 0).  A frame costs
+ * min(2 c + 1, n) comparisons.  col >= n_cols, stride < n_cols or a null pointer
+ * with work to do is MP3G_ERR_INVALID_ARGUMENT.
+ *
+ * Selection.  out: float [n_rows][n_planes][n_frames_out][stride_out], stride_out
+ * >= n_cols, not overlapping in.  With m = min(the number of t < n with
+ * voiced[t] != 0, n_frames_out): out[j][0..n_cols) is a copy of the j-th such
+ * frame for j < m and +0 for m <= j < n_frames_out, so the batch stays dense and
+ * zero-padded; words at columns >= n_cols are never written; lengths_out
+ * (uint32 [n_rows][n_planes]) = m. */
+#define MP3G_SCMN_CENTER 1u
+#define MP3G_SCMN_NORM_VARS 2u
+int mp3g_sliding_cmn_rows(int device, const float* d_in, float* d_out, uint32_t n_rows, uint32_t n_planes,
+                          uint32_t n_frames, uint32_t stride, uint32_t n_cols, const uint32_t* d_lengths,
+                          uint32_t cmn_window, uint32_t min_window, uint32_t flags, void* hip_stream);
+int mp3g_sliding_cmn_host(const float* in, float* out, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames,
+                          uint32_t stride, uint32_t n_cols, const uint32_t* lengths, uint32_t cmn_window,
+                          uint32_t min_window, uint32_t flags);
+int mp3g_vad_energy_rows(int device, const float* d_feats, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames,
+                         uint32_t stride, uint32_t n_cols, uint32_t col, const uint32_t* d_lengths,
+                         float energy_threshold, float energy_mean_scale, float proportion_threshold,
+                         uint32_t frames_context, uint8_t* d_voiced, uint32_t* d_counts, void* hip_stream);
+int mp3g_vad_energy_host(const float* feats, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames, uint32_t stride,
+                         uint32_t n_cols, uint32_t col, const uint32_t* lengths, float energy_threshold,
+                         float energy_mean_scale, float proportion_threshold, uint32_t frames_context,
+                         uint8_t* voiced, uint32_t* counts);
+int mp3g_select_frames_rows(int device, const float* d_in, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames,
+                            uint32_t stride, uint32_t n_cols, const uint8_t* d_voiced, const uint32_t* d_lengths,
+                            float* d_out, uint32_t n_frames_out, uint32_t stride_out, uint32_t* d_lengths_out,
+                            void* hip_stream);
+int mp3g_select_frames_host(const float* in, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames, uint32_t stride,
+                            uint32_t n_cols, const uint8_t* voiced, const uint32_t* lengths, float* out,
+                            uint32_t n_frames_out, uint32_t stride_out, uint32_t* lengths_out);
 
 /* ---- Integrated loudness of decoded rows ----------------------------------------
  * ITU-R BS.1770-4 integrated loudness (what libebur128, pyloudnorm and ffmpeg's
