@@ -75,6 +75,12 @@ class _Reader(C.Structure):
     _fields_ = [("read", READ_FN), ("seek", SEEK_FN), ("user", C.c_void_p)]
 
 
+class _AugmentArgs(C.Structure):  # include/mp3g.h mp3g_augment_args
+    _fields_ = ([(k, C.c_void_p) for k in ("x", "out", "lengths", "rir_index", "noise", "noise_lengths",
+                                            "noise_power", "slots", "stats")]
+                + [(k, C.c_uint32) for k in ("n_rows", "n_planes", "T", "n_noise", "Tn", "A", "flags", "zero")])
+
+
 class Mp3gError(RuntimeError):
     def __init__(self, status, msg=""):
         super().__init__(f"mp3g status {status} ({STATUS.get(status, '?')}): {msg}")
@@ -228,6 +234,22 @@ def lib():
             L.mp3g_loudness_range_rows.argtypes = [vp, u32, u32, u32, vp, vp, u32, vp, vp, vp, vp]
             L.mp3g_gain_rows_peak.argtypes = [C.c_int, vp, u32, u32, u32, vp, vp, C.c_double, C.c_float, vp, vp, vp]
             L.mp3g_gain_host_peak.argtypes = [vp, u32, u32, u32, vp, vp, C.c_double, C.c_float, vp, vp]
+        if hasattr(L, "mp3g_augment_rows"):
+            L.mp3g_reverb_create.argtypes = [C.c_int, C.c_int, vp, u32, u32, vp, C.POINTER(vp)]
+            L.mp3g_reverb_free.argtypes = [vp]
+            L.mp3g_reverb_free.restype = None
+            L.mp3g_reverb_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), C.POINTER(vp),
+                                           C.POINTER(vp), C.POINTER(u64)]
+            L.mp3g_reverb_read_spectra.argtypes = [vp, vp]
+            L.mp3g_reverb_scratch_bytes.argtypes = [vp, u32, u32, u32]
+            L.mp3g_reverb_scratch_bytes.restype = u64
+            L.mp3g_augment_host.argtypes = [vp, C.POINTER(_AugmentArgs)]
+            L.mp3g_augment_rows.argtypes = [vp, C.c_int, C.POINTER(_AugmentArgs), vp, vp, vp, vp, u64, vp]
+            L.mp3g_augment_debug_launch.argtypes = L.mp3g_augment_rows.argtypes + [u32]
+            L.mp3g_row_power_scratch_bytes.argtypes = [u32, u32]
+            L.mp3g_row_power_scratch_bytes.restype = u64
+            L.mp3g_row_power_host.argtypes = [vp, u32, u32, vp, vp]
+            L.mp3g_row_power_rows.argtypes = [C.c_int, vp, u32, u32, vp, vp, vp, vp]
         L.mp3g_lame_parse.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo)]
         L.mp3g_lame_parse_reader.argtypes = [vp, C.c_size_t, C.POINTER(_LameInfo), C.POINTER(C.c_size_t)]
         L.mp3g_lame_total_delay.argtypes = [C.POINTER(_LameInfo)]
@@ -2017,6 +2039,334 @@ def decode_windows_normalized_tensor(datas, starts, n_samples, target_lufs=-23.0
         return tuple(res) + (stats, gains)
     true_peaks = np.zeros(B, np.float32) if d_tp is None else d_tp.cpu().numpy()
     return tuple(res) + (stats, gains, Loudness.range_stats(d_range), true_peaks)
+
+
+# ---- room reverberation and noise at an SNR (include/mp3g.h) -------------------
+AUGMENT_NORMALIZE = 1
+AUGMENT_MAX_SLOTS = 8
+AUGMENT_SLOT_DTYPE = np.dtype([("noise_index", "<i4"), ("start", "<u4"), ("offset", "<u4"), ("wrap", "<u4"),
+                               ("snr_ratio", "<f8")])
+assert AUGMENT_SLOT_DTYPE.itemsize == 24 and C.sizeof(_AugmentArgs) == 104
+_AUGMENT_KEYS = ("reverb", "rir_index", "noise", "noise_lengths", "noise_power", "additive", "normalize", "out",
+                 "stats", "stream")
+
+
+class Reverb:
+    """A bank of room impulse responses for augment (mp3g_reverb_*): rirs float32
+    [R, S] (or one response [S]), rir_lengths the taps of each (None: S), 1 ..
+    65,536, at `rate` (20 .. 384000 Hz).  Per response the peak (the first index of the largest
+    value), the early window [es, ee) = [peak - rate // 1000, peak + rate // 20)
+    cut to the response, and the spectra of its P = ceil(L / 1024) partitions of
+    h + i h_early, which one partitioned overlap-save pipeline turns into the
+    reverberated signal and the early-reverberation energy.  device=None (or
+    -1) makes a host-only object."""
+
+    def __init__(self, rirs, rir_lengths=None, rate=16000, device=0):
+        h = np.ascontiguousarray(rirs, dtype=np.float32)
+        if h.ndim == 1:
+            h = h[None]
+        if h.ndim != 2:
+            raise ValueError("Reverb: rirs is [R, S] or [S]")
+        R, stride = h.shape
+        ln = (np.full(R, stride, np.uint32) if rir_lengths is None else
+              np.ascontiguousarray(np.clip(np.asarray(rir_lengths, dtype=np.int64), 0, 2 ** 32 - 1), dtype=np.uint32))
+        if ln.shape != (R,):
+            raise ValueError("Reverb: one length per response")
+        self._h = C.c_void_p()
+        self.device = -1 if device is None else int(device)
+        self.rate = int(rate)
+        _check(lib().mp3g_reverb_create(self.device, self.rate, _ptr(h) if h.size else None, R, stride,
+                                        _ptr(ln) if R else None, C.byref(self._h)))
+        n, lmax, ns = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        p = [C.c_void_p() for _ in range(3)]
+        _check(lib().mp3g_reverb_info(self._h, C.byref(n), C.byref(lmax), C.byref(p[0]), C.byref(p[1]), C.byref(p[2]),
+                                      C.byref(ns)))
+        self.n_rirs, self.max_taps, self.n_spectra = n.value, lmax.value, ns.value
+        # views of the library's tables: valid while this object lives
+        self._table = np.ctypeslib.as_array(C.cast(p[0], C.POINTER(C.c_uint32)), shape=(self.n_rirs, 8))
+        self.twiddles = np.ctypeslib.as_array(C.cast(p[1], C.POINTER(C.c_float)), shape=(4096, 2))
+        self._spectra = np.ctypeslib.as_array(C.cast(p[2], C.POINTER(C.c_float)), shape=(self.n_spectra, 2))
+
+    def info(self):
+        """Per response: L, peak, es, ee, P (int64 arrays [R]) and offset, where
+        its first partition's 2,048 slots start in spectra()."""
+        t = self._table.astype(np.int64)
+        return {"L": t[:, 0], "peak": t[:, 1], "es": t[:, 2], "ee": t[:, 3], "P": t[:, 4],
+                "offset": t[:, 6] | (t[:, 7] << 32)}
+
+    def spectra(self):
+        """The host copy of the partition spectra, float32 [n_spectra, 2], bins in slot order."""
+        return self._spectra.copy()
+
+    def device_spectra(self):
+        """What the device holds of them (mp3g_reverb_read_spectra; synchronous)."""
+        out = np.empty((self.n_spectra, 2), np.float32)
+        _check(lib().mp3g_reverb_read_spectra(self._h, _ptr(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            self._table = self.twiddles = self._spectra = None
+            lib().mp3g_reverb_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _row_lengths(lengths, B, what):
+    if lengths is None:
+        return None
+    ln = np.ascontiguousarray(np.clip(np.asarray(lengths, dtype=np.int64), 0, 2 ** 32 - 1), dtype=np.uint32)
+    if ln.shape != (B,):
+        raise ValueError(what + ": one length per row")
+    return ln
+
+
+def row_power_host(x, lengths=None):
+    """The reference on the CPU (mp3g_row_power_host): sum(v^2) / len of every
+    row of the float32 array x [B, T] over its first min(lengths[b], T) samples,
+    float64 in include/mp3g.h's blocked order (a row of no samples: 0)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("row_power_host: x is [B, T]")
+    B, T = x.shape
+    ln = _row_lengths(lengths, B, "row_power_host")
+    power = np.zeros(B, np.float64)
+    _check(lib().mp3g_row_power_host(_ptr(x) if x.size else None, B, T, _ptr(ln) if ln is not None and B else None,
+                                     _ptr(power) if B else None))
+    return power
+
+
+_aug_scratch = {}  # per device: the scratch of the last call (grown, never shrunk)
+_aug_keep = {}  # per device: the last call's small tensors, alive while its launches may run
+
+
+def _scratch_for(dev, need):
+    import torch
+    scratch = _aug_scratch.get(dev)
+    if scratch is None or scratch.numel() * 8 < need:
+        if scratch is not None:  # launches of an earlier call, on whatever stream, may still use the old one
+            torch.cuda.synchronize(dev)
+        scratch = _aug_scratch[dev] = torch.empty(max(1, (need + 7) // 8), dtype=torch.float64, device=dev)
+    return scratch
+
+
+def row_power(d_x, lengths=None, stream=None, d_out=None):
+    """The device call (mp3g_row_power_rows): as row_power_host states it and
+    bit for bit, of the contiguous float32 device tensor d_x [B, T].  Returns a
+    float64 device tensor [B] (d_out when given).  Two launches, asynchronous on
+    `stream` (None = the current torch stream); the scratch is a tensor kept per
+    device, shared with augment, so calls on one device must be stream-ordered."""
+    import torch
+    if (not torch.is_tensor(d_x) or d_x.dtype != torch.float32 or not d_x.is_contiguous() or not d_x.is_cuda
+            or d_x.dim() != 2):
+        raise ValueError("row_power: a contiguous float32 device tensor [B, T]")
+    B, T = int(d_x.shape[0]), int(d_x.shape[1])
+    dev = d_x.device
+    if d_out is None:
+        d_out = torch.zeros(B, dtype=torch.float64, device=dev)
+    if (not torch.is_tensor(d_out) or d_out.dtype != torch.float64 or not d_out.is_contiguous()
+            or d_out.device != dev or tuple(d_out.shape) != (B,)):
+        raise ValueError("row_power: d_out is a contiguous float64 tensor [B] on d_x's device")
+    d_len = _device_lengths(lengths, B, dev, "row_power")
+    need = int(lib().mp3g_row_power_scratch_bytes(B, T))
+    scratch = _scratch_for(dev, need)
+    _aug_keep[dev] = (d_len,)
+    _check(lib().mp3g_row_power_rows(dev.index or 0, _dptr(d_x), B, T, None if d_len is None else _dptr(d_len),
+                                     _dptr(scratch), _dptr(d_out), _stream_of(d_x, stream)))
+    return d_out
+
+
+def _augment_slots(additive, B):
+    """additive (a dict of [B, A] arrays: index, snr_db, start, offset, wrap) as
+    mp3g_augment_slot records [B, A]; snr_ratio = 10^(-snr_db / 10) in float64."""
+    if additive is None:
+        return np.zeros((B, 0), AUGMENT_SLOT_DTYPE)
+    unknown = set(additive) - {"index", "snr_db", "start", "offset", "wrap"}
+    if unknown or "index" not in additive:
+        raise ValueError("augment: additive holds index and optionally snr_db, start, offset, wrap")
+    idx = np.asarray(additive["index"], dtype=np.int64)
+    if idx.ndim == 1:
+        idx = idx[:, None]
+    if idx.ndim != 2 or idx.shape[0] != B:
+        raise ValueError("augment: additive arrays are [B, A]")
+    s = np.zeros(idx.shape, AUGMENT_SLOT_DTYPE)
+
+    def field(key, dtype):
+        v = np.asarray(additive.get(key, 0), dtype=dtype)
+        return np.broadcast_to(v[:, None] if v.ndim == 1 and idx.shape[1] != v.shape[0] else v, idx.shape)
+    s["noise_index"] = np.clip(idx, -1, 2 ** 31 - 1)
+    s["snr_ratio"] = np.power(10.0, -field("snr_db", np.float64) / 10.0)
+    for key, name in (("start", "start"), ("offset", "offset")):
+        v = field(key, np.int64)
+        if (v < 0).any():
+            raise ValueError("augment: a negative " + key)
+        s[name] = np.minimum(v, 2 ** 32 - 1)
+    s["wrap"] = field("wrap", np.int64) != 0
+    return s
+
+
+def augment_host(x, lengths=None, reverb=None, rir_index=None, noise=None, noise_lengths=None, noise_power=None,
+                 additive=None, normalize=True):
+    """The reference on the CPU (mp3g_augment_host; Kaldi's wav-reverberate is
+    the model): x float32 [B, C, T] (C = 1 or 2) or [B, T], over each row's first
+    n = min(lengths[b], T) samples.  Row b is convolved with response
+    rir_index[b] of `reverb` (< 0 or None: none) and shifted by the response's
+    peak, so the length stays n; then for each slot of additive (a dict of
+    [B, A] arrays, A <= 8: index into the float32 noise bank noise [M, Tn], < 0:
+    none; snr_db; start in output samples; offset into the noise; wrap) the
+    noise is added with the gain sqrt(10^(-snr_db / 10) signal_power /
+    noise_power), signal_power the EARLY reverberation's (the row's own power
+    without a response) and noise_power [M] row_power_host of the bank unless
+    given; with normalize the result is scaled back to the row's power.  Every
+    plane gets the row's response and noises; the powers are per plane.
+    Returns (out like x, +0 past n; stats float64 [B, C, 4] or [B, 4]:
+    power_before, signal_power, power_after, scale)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim not in (2, 3):
+        raise ValueError("augment_host: x is [B, C, T] or [B, T]")
+    B, T = x.shape[0], x.shape[-1]
+    planes = x.shape[1] if x.ndim == 3 else 1
+    ln = _row_lengths(lengths, B, "augment_host")
+    ri = None
+    if rir_index is not None:
+        ri = np.ascontiguousarray(np.clip(np.asarray(rir_index, dtype=np.int64), -1, 2 ** 31 - 1), dtype=np.int32)
+        if ri.shape != (B,):
+            raise ValueError("augment_host: one rir_index per row")
+    nz = nl = npow = None
+    if noise is not None:
+        nz = np.ascontiguousarray(noise, dtype=np.float32)
+        if nz.ndim != 2:
+            raise ValueError("augment_host: noise is [M, Tn]")
+        nl = _row_lengths(np.full(len(nz), nz.shape[1]) if noise_lengths is None else noise_lengths, len(nz),
+                          "augment_host (noise)")
+        npow = (row_power_host(nz, nl) if noise_power is None else
+                np.ascontiguousarray(noise_power, dtype=np.float64))
+        if npow.shape != (len(nz),):
+            raise ValueError("augment_host: one noise_power per noise")
+    slots = _augment_slots(additive, B)
+    out = np.zeros_like(x)
+    stats = np.zeros((B, planes, 4), np.float64)
+    a = _AugmentArgs()
+    a.x, a.out, a.lengths, a.rir_index = _ptr(x) if x.size else None, _ptr(out) if x.size else None, _ptr(ln), _ptr(ri)
+    if nz is not None and len(nz):
+        a.noise, a.noise_lengths, a.noise_power = _ptr(nz) if nz.size else None, _ptr(nl), _ptr(npow)
+        a.n_noise, a.Tn = nz.shape
+    a.slots = _ptr(slots) if slots.size else None
+    a.stats = _ptr(stats) if stats.size else None
+    a.n_rows, a.n_planes, a.T, a.A = B, planes, T, slots.shape[1]
+    a.flags = AUGMENT_NORMALIZE if normalize else 0
+    _check(lib().mp3g_augment_host(reverb._h if reverb is not None else None, C.byref(a)))
+    return out, (stats if x.ndim == 3 else stats[:, 0])
+
+
+def augment(d_x, lengths=None, reverb=None, rir_index=None, noise=None, noise_lengths=None, noise_power=None,
+            additive=None, normalize=True, out=None, stats=None, stream=None, _launch=None):
+    """The device call (mp3g_augment_rows): as augment_host states it and bit
+    for bit, out and stats, from the contiguous float32 device tensor d_x
+    [B, C, T] or [B, T] into `out` (another tensor like it, not overlapping;
+    made here when None).  noise is a float32 device tensor [M, Tn] (an array is
+    uploaded), noise_power a float64 device tensor [M] (None: row_power of the
+    bank); lengths as for true_peak; rir_index, noise_lengths and additive are
+    host arrays, uploaded here.  Five launches whose shapes depend on B, C, T
+    and the bank's longest response only, asynchronous on `stream` (None = the
+    current torch stream); the scratch is a tensor kept per device, so calls on
+    one device must be stream-ordered (a call that needs a larger one
+    synchronises the device before the old one is released).  Returns (out, stats float64 device
+    tensor [B, C, 4] or [B, 4])."""
+    import torch
+    if (not torch.is_tensor(d_x) or d_x.dtype != torch.float32 or not d_x.is_contiguous() or not d_x.is_cuda
+            or d_x.dim() not in (2, 3)):
+        raise ValueError("augment: a contiguous float32 device tensor [B, C, T] or [B, T]")
+    B, T = int(d_x.shape[0]), int(d_x.shape[-1])
+    planes = int(d_x.shape[1]) if d_x.dim() == 3 else 1
+    dev = d_x.device
+    if out is None:
+        out = torch.empty_like(d_x)
+    if (not torch.is_tensor(out) or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != d_x.shape
+            or out.device != dev):
+        raise ValueError("augment: out is a contiguous float32 tensor like d_x")
+    stats_shape = (B, planes, 4) if d_x.dim() == 3 else (B, 4)
+    if stats is None:
+        stats = torch.zeros(stats_shape, dtype=torch.float64, device=dev)
+    if (not torch.is_tensor(stats) or stats.dtype != torch.float64 or not stats.is_contiguous()
+            or tuple(stats.shape) != stats_shape or stats.device != dev):
+        raise ValueError("augment: stats is a contiguous float64 tensor [B, C, 4] (or [B, 4]) on d_x's device")
+    d_len = _device_lengths(lengths, B, dev, "augment")
+    ri = d_ri = None
+    if rir_index is not None:
+        ri = np.ascontiguousarray(np.clip(np.asarray(rir_index, dtype=np.int64), -1, 2 ** 31 - 1), dtype=np.int32)
+        if ri.shape != (B,):
+            raise ValueError("augment: one rir_index per row")
+        d_ri = torch.from_numpy(ri).to(dev)
+    nl = d_nl = d_np = None
+    M = Tn = 0
+    if noise is not None:
+        if not torch.is_tensor(noise):
+            noise = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)).to(dev)
+        if (noise.dtype != torch.float32 or not noise.is_contiguous() or noise.device != dev or noise.dim() != 2):
+            raise ValueError("augment: noise is a contiguous float32 tensor [M, Tn] on d_x's device")
+        M, Tn = int(noise.shape[0]), int(noise.shape[1])
+        nl = _row_lengths(np.full(M, Tn) if noise_lengths is None else noise_lengths, M, "augment (noise)")
+        nl = np.minimum(nl, Tn)
+        d_nl = torch.from_numpy(nl.astype(np.int32)).to(dev)
+        if noise_power is None:
+            d_np = row_power(noise, d_nl, stream=stream)
+        elif torch.is_tensor(noise_power):
+            d_np = noise_power
+        else:
+            d_np = torch.from_numpy(np.ascontiguousarray(noise_power, dtype=np.float64)).to(dev)
+        if (d_np.dtype != torch.float64 or not d_np.is_contiguous() or d_np.device != dev
+                or tuple(d_np.shape) != (M,)):
+            raise ValueError("augment: noise_power is a contiguous float64 tensor [M] on d_x's device")
+    slots = _augment_slots(additive, B)
+    d_slots = torch.from_numpy(slots.view(np.uint8).reshape(-1).copy()).to(dev) if slots.size else None
+    h = reverb._h if reverb is not None else None
+    need = int(lib().mp3g_reverb_scratch_bytes(h, B, planes, T))
+    scratch = _scratch_for(dev, need)
+    _aug_keep[dev] = (d_len, d_ri, d_nl, d_np, d_slots, noise)
+
+    def p(t):
+        return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    a = _AugmentArgs()
+    a.x, a.out, a.lengths, a.rir_index = p(d_x), p(out), p(d_len), p(d_ri)
+    if M:
+        a.noise, a.noise_lengths, a.noise_power = p(noise), p(d_nl), p(d_np)
+        a.n_noise, a.Tn = M, Tn
+    a.slots, a.stats = p(d_slots), p(stats)
+    a.n_rows, a.n_planes, a.T, a.A = B, planes, T, slots.shape[1]
+    a.flags = AUGMENT_NORMALIZE if normalize else 0
+    call = (h, dev.index or 0, C.byref(a), _ptr(ri), _ptr(nl) if M else None, _ptr(slots) if slots.size else None,
+            p(scratch), scratch.numel() * 8, _stream_of(d_x, stream))
+    if _launch is None:
+        _check(lib().mp3g_augment_rows(*call))
+    else:  # (diagnostic: one launch of the five, for timing)
+        _check(lib().mp3g_augment_debug_launch(*call, int(_launch)))
+    return out, stats
+
+
+def decode_windows_augmented_tensor(datas, starts, n_samples, rate, mode=MODE_EXACT, out_format=OUT_F32_PLANAR,
+                                    gapless=False, quality="fast", n_threads=0, device=0, **augment_keywords):
+    """decode_windows_resampled_tensor, then augment on its batch and lengths
+    with the keywords of augment (reverb, rir_index, noise, noise_lengths,
+    noise_power, additive, normalize, out, stats, stream): the augmented
+    training batch at one sample rate with no copy to the host; it equals
+    augment_host of the resampled tensor bit for bit.  Returns (out, lengths,
+    end_status, rates, stats).  Without any augment keyword it is
+    decode_windows_resampled_tensor, and returns what that returns."""
+    unknown = set(augment_keywords) - set(_AUGMENT_KEYS)
+    if unknown:
+        raise TypeError("decode_windows_augmented_tensor: unknown keyword " + sorted(unknown)[0])
+    res = decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=mode, out_format=out_format,
+                                          gapless=gapless, quality=quality, n_threads=n_threads, device=device)
+    if not augment_keywords:
+        return res
+    out, stats = augment(res[0], res[1], **augment_keywords)
+    return (out,) + tuple(res[1:]) + (stats,)
 
 
 # ---- STFT and mel spectrograms of decoded rows (include/mp3g.h) ----------------

@@ -1200,6 +1200,134 @@ int mp3g_gain_host_peak(float* x, uint32_t n_rows, uint32_t n_planes, uint32_t T
                         const mp3g_loudness_stats* stats, double target_energy, float peak_ceiling, float* gain_out,
                         const float* peak);
 
+/* ---- Room reverberation and noise at an SNR -------------------------------------
+ * The augmentation Kaldi's x-vector recipes train on (wav-reverberate is the
+ * model): a batch float [n_rows][n_planes][T], n_planes 1 or 2, is convolved row
+ * by row with a room impulse response (RIR), has noises added at signal-to-noise
+ * ratios measured against the EARLY reverberation, and is brought back to its
+ * power.  Every plane of a row gets the row's RIR and noises; every power is per
+ * (row, plane).  n = min(lengths[r], T) below (lengths NULL: T).  Deliberately
+ * unlike the tool: only the shifted output of the input's length, a noise's
+ * start counted on the output's timeline, powers per plane.  NOT offered: speed
+ * and volume perturbation, multi-channel RIRs, an output length that depends on
+ * the data.
+ *
+ * The sums.  Every power is a float64 sum of exact products (double)a *
+ * (double)a in ONE order: the samples are cut into blocks of 1,024, a block's
+ * products are added ascending from +0.0, then the block sums ascending from
+ * +0.0; power = sum / count, an IEEE float64 division (count 0: +0.0).  The
+ * blocks of x, of a noise row and of the mixed signal start at the row's sample
+ * 0; those of the early reverberation are the blocks [1024 k, 1024 k + 1024) of
+ * the full convolution's timeline, cut to [es, n + ee - 1).
+ * mp3g_row_power_rows / _host: power[r] = that of x[r][0 .. min(lengths[r], T))
+ * for float [n_rows][T] -- the noise bank's Pn.  Two launches, d_scratch of
+ * mp3g_row_power_scratch_bytes (8-byte aligned).
+ *
+ * mp3g_reverb_create(device, rate, rirs, n_rirs, stride, rir_lengths): a bank of
+ * n_rirs >= 1 responses, host float [n_rirs][stride], response i of L =
+ * rir_lengths[i] taps, 1 <= L <= 65,536 and L <= stride (else
+ * MP3G_ERR_INVALID_ARGUMENT), rate 20 .. 384000 (outside: MP3G_ERR_UNSUPPORTED;
+ * rate <= 0: MP3G_ERR_INVALID_ARGUMENT; below 20 Hz the early window would be
+ * empty); device = -1 makes a host-only object.  Per response h:
+ *   peak = the first index of the largest VALUE (not magnitude; h[j] > h[peak],
+ *          j ascending)
+ *   es = max(0, peak - rate / 1000),  ee = min(L, peak + rate / 20)  (integer
+ *        divisions: the truncations of 0.001 rate and 0.05 rate)
+ *   h_e = h on [es, ee), 0 elsewhere: the early response
+ *   P = ceil(L / 1024) partitions;  G_p = FFT_2048 of g_p[j] = h[1024 p + j] +
+ *       i h_e[1024 p + j] for j < 1024 (0 past L), 0 for j >= 1024
+ * The transform is go-mp3_amd/csrc/reverb_fft.h's: the STFT's float32
+ * decimation-in-frequency network (2,048 complex points, twiddles exp(-2 pi i k /
+ * 4096) from float64, rounded once), bins left in slot order.  mp3g_reverb_info:
+ * the table [n_rirs][8] words L, peak, es, ee, P, 0 and the 64-bit offset of G_0
+ * in the spectra (complex values), the twiddles [4096][2], the spectra
+ * [n_spectra][2]; any pointer may be NULL.  mp3g_reverb_read_spectra copies the
+ * DEVICE's spectra to host (synchronous; for tests).
+ *
+ * mp3g_augment_args.  x, out, lengths (may be NULL), rir_index (int32 [n_rows],
+ * may be NULL: no row has a response; < 0: this row has none), noise (float
+ * [n_noise][Tn]), noise_lengths (uint32 [n_noise], clamped to Tn), noise_power
+ * (double [n_noise], mp3g_row_power_*), slots (mp3g_augment_slot [n_rows][A], A
+ * <= 8) and stats (double [n_rows][n_planes][4]) are host pointers for
+ * mp3g_augment_host and device pointers for mp3g_augment_rows, which takes host
+ * copies of rir_index, noise_lengths and slots beside them for its checks.  A
+ * slot: noise_index (< 0: none), snr_ratio = 10^(-snr_dB / 10) formed by the
+ * caller in float64 (no pow runs on the device), start in output samples,
+ * offset < the noise's length, wrap (non-zero: the noise repeats cyclically to
+ * the row's end; zero: it adds min(len - offset, n - start) samples).
+ *
+ * Per (row, plane):
+ *   1 power_before = power of x[0 .. n)
+ *   2 with a response: y[o] = (x * h)[o + peak], 0 <= o < n (the tool's
+ *     --shift-output=true);  signal_power = sum over t in [es, n + ee - 1) of
+ *     (x * h_e)[t]^2 / (n + (ee - es) - 1).  Without: y = x as bits and
+ *     signal_power = power_before.
+ *     The convolutions, float32 in one order: with NB = ceil(n / 1024), X_m =
+ *     FFT_2048 of (x[1024 (m - 1) + j], 0), j < 2048, 0 <= m <= NB (x = 0 outside
+ *     [0, n)); for output block k in [es / 1024, (n + ee - 2) / 1024]:
+ *       acc = (+0, +0);  for p ascending, max(0, k - NB) <= p <= min(P - 1, k):
+ *         acc += X_(k-p) G_p slot by slot, a product (a + i b)(c + i d) as t = b d,
+ *         re = fmaf(a, c, -t), u = b c, im = fmaf(a, d, u), then one float32
+ *         addition per part
+ *       z = the transposed (decimation-in-time) network of reverb_fft.h on acc,
+ *       conjugated twiddles, slot order in, natural order out;  for j < 1024, t =
+ *       1024 k + j:  (x * h)[t] = z[1024 + j].re * 2^-11,  (x * h_e)[t] = z[1024 +
+ *       j].im * 2^-11
+ *   3 v = y;  for the slots in ascending order, skipping noise_index < 0 and Pn ==
+ *     0:  g = (float)sqrt(snr_ratio * signal_power / Pn) (the product first; IEEE
+ *     float64), and for start <= j < n with the slot's noise sample at offset + (j -
+ *     start) (modulo len with wrap; none past len without): v[j] = fmaf(g, noise, v[j])
+ *   4 power_after = power of v[0 .. n);  with MP3G_AUGMENT_NORMALIZE: scale =
+ *     sqrt(power_before / power_after), 1.0 where power_after == 0 or n == 0, and
+ *     out[j] = (float)((double)v[j] * scale); without: scale = 1.0 and out = v as
+ *     bits.  out[j] = +0 for n <= j < T.
+ *   stats = power_before, signal_power, power_after, scale.
+ * out is out of place: overlapping x is MP3G_ERR_INVALID_ARGUMENT, as are A > 8,
+ * an unknown flag, rir_index >= n_rirs (or >= 0 without an object), noise_index
+ * >= n_noise, offset >= the noise's length and a null buffer with work to do;
+ * all before any device call.  No rows or T == 0 is MP3G_OK with nothing done.
+ *
+ * mp3g_augment_rows equals mp3g_augment_host bit for bit, out and stats.  Five
+ * launches whose shapes depend on n_rows, n_planes, T and the object's longest
+ * response only, no atomics, no allocation, asynchronous on hip_stream and
+ * graph-capturable; d_scratch of at least mp3g_reverb_scratch_bytes(rv, ...)
+ * bytes (8-byte aligned; rv may be NULL for a call without responses), a smaller
+ * scratch_bytes or a NULL scratch is MP3G_ERR_INVALID_ARGUMENT. */
+#define MP3G_AUGMENT_NORMALIZE 1u
+typedef struct mp3g_reverb mp3g_reverb;
+typedef struct mp3g_augment_slot {
+  int32_t noise_index;
+  uint32_t start, offset, wrap;
+  double snr_ratio;
+} mp3g_augment_slot; /* 24 bytes */
+typedef struct mp3g_augment_args {
+  const float* x;
+  float* out;
+  const uint32_t* lengths;
+  const int32_t* rir_index;
+  const float* noise;
+  const uint32_t* noise_lengths;
+  const double* noise_power;
+  const mp3g_augment_slot* slots;
+  double* stats;
+  uint32_t n_rows, n_planes, T, n_noise, Tn, A, flags, zero;
+} mp3g_augment_args;
+int mp3g_reverb_create(int device, int rate, const float* rirs, uint32_t n_rirs, uint32_t stride,
+                       const uint32_t* rir_lengths, mp3g_reverb** out);
+void mp3g_reverb_free(mp3g_reverb* rv);
+int mp3g_reverb_info(const mp3g_reverb* rv, uint32_t* n_rirs, uint32_t* max_taps, const uint32_t** table,
+                     const float** twiddles, const float** spectra, uint64_t* n_spectra);
+int mp3g_reverb_read_spectra(const mp3g_reverb* rv, float* spectra);
+uint64_t mp3g_reverb_scratch_bytes(const mp3g_reverb* rv, uint32_t n_rows, uint32_t n_planes, uint32_t T);
+int mp3g_augment_host(const mp3g_reverb* rv, const mp3g_augment_args* args);
+int mp3g_augment_rows(const mp3g_reverb* rv, int device, const mp3g_augment_args* d_args, const int32_t* rir_index,
+                      const uint32_t* noise_lengths, const mp3g_augment_slot* slots, void* d_scratch,
+                      uint64_t scratch_bytes, void* hip_stream);
+uint64_t mp3g_row_power_scratch_bytes(uint32_t n_rows, uint32_t T);
+int mp3g_row_power_host(const float* x, uint32_t n_rows, uint32_t T, const uint32_t* lengths, double* power);
+int mp3g_row_power_rows(int device, const float* d_x, uint32_t n_rows, uint32_t T, const uint32_t* d_lengths,
+                        void* d_scratch, double* d_power, void* hip_stream);
+
 /* ---- STFT and mel spectrograms of decoded rows --------------------------------
  * The front ends of music and general audio at its native rate: an STFT by FFT
  * for n_fft = P in {256, 512, 1024, 2048, 4096}, stored as complex bins, power
@@ -1389,6 +1517,16 @@ int mp3g_plan_debug_timeline(mp3g_plan* plan, const mp3g_granule* d_granules, co
  * whether it saw the flag.  Asynchronous. */
 int mp3g_debug_clock_probe(int device, const uint32_t* d_flag, uint64_t* d_out, uint32_t n_waves,
                            uint32_t max_ms, void* hip_stream);
+
+/* One launch of mp3g_augment_rows, which = 0 .. 4 (the power of x, the forward
+ * transforms, the convolution, the mix, the scale), with that call's arguments
+ * and checks: for timing a launch on buffers a whole call has filled
+ * (tools/reverb_time.py).  Run alone, the mix and the scale work on what `out`
+ * holds, so the samples are no longer the contract's. */
+int mp3g_augment_debug_launch(const mp3g_reverb* rv, int device, const mp3g_augment_args* d_args,
+                              const int32_t* rir_index, const uint32_t* noise_lengths,
+                              const mp3g_augment_slot* slots, void* d_scratch, uint64_t scratch_bytes,
+                              void* hip_stream, uint32_t which);
 
 /* ---- Xing / Info / LAME tag (lameinfo/lameinfo.go) ----
  * The reference's lameinfo package: the tag in the first frame (encoder delay
