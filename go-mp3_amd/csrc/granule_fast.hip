@@ -1309,7 +1309,7 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
     if (out) {
       f2 acc2[9];
       window_acc(par, acc2);
-      pack_pcm(acc2, nch, pk);
+      pack_pcm_sat(acc2, nch, pk);
       // stored right away: a store's data registers are free again once it
       // has issued (no s_waitcnt before their reuse on gfx950), and the loads
       // this wave waits for next were issued before these stores
@@ -1649,12 +1649,27 @@ granule_fast_kernel(const ChunkDesc* __restrict__ chunks, uint32_t n_chunks, con
         up[i] = xl::from_prev(x[17 - i]);  // x_{k-1}[17-i]
         dn[i] = xl::from_next(x[i]);       // x_{k+1}[i]
       }
+      // The neighbours' share on every lane (a DPP read of a lane that EXEC
+      // disables returns the bound_ctrl zero, so the fetches above and these
+      // products stay unmasked), then the butterfly on the line where it
+      // lies, under the lane mask: x = cs x +- t, the product and the FMA of
+      // the sum written out.  Lanes at the edge of a channel or outside the
+      // butterflies' subbands keep their registers: no select.  (asm volatile:
+      // the compiler may not turn the branch back into selects.)
 #pragma unroll
       for (int i = 0; i < 8; i++) {
-        const float cs = g_fast.aa_cs[i], ca = g_fast.aa_ca[i];
-        const float ui = x[i], li = x[17 - i];
-        x[i] = self(lower, ui * cs + up[i] * ca, ui);
-        x[17 - i] = self(upper, li * cs - dn[i] * ca, li);
+        up[i] *= g_fast.aa_ca[i];
+        dn[i] *= g_fast.aa_ca[i];
+      }
+      if (lower) {
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+          asm volatile("v_fma_f32 %0, %1, %0, %2" : "+v"(x[i]) : "s"(g_fast.aa_cs[i]), "v"(up[i]));
+      }
+      if (upper) {
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+          asm volatile("v_fma_f32 %0, %1, %0, -%2" : "+v"(x[17 - i]) : "s"(g_fast.aa_cs[i]), "v"(dn[i]));
       }
     }
 

@@ -67,6 +67,44 @@ __device__ __forceinline__ void pack_pcm(const f2 acc2[9], int nch, uint32_t pk[
   else pack(std::true_type{});
 }
 
+// The same dwords with the clamp made by the integer pack (the fast kernel's
+// s16 path): the sums truncated to int32 first (v_cvt_i32_f32, which
+// saturates at the int32 range), swapped as integers, then one
+// v_cvt_pk_i16_i32 of (L, R) -- it saturates each half to [-32768, 32767] --
+// and one v_pk_max_i16 that lifts -32768 to -32767: int(sum * 32767) clamped
+// to +-32767 for every finite sum, as above, without the two float clamps per
+// slot pair.  (Swap first, pack last: packed before the swap, the swap's tied
+// operands cost copies)
+__device__ __forceinline__ void pack_pcm_sat(const f2 acc2[9], int nch, uint32_t pk[9]) {
+  typedef short s2 __attribute__((ext_vector_type(2)));
+  // (the swap in front of the channel-count branch: inside it, each branch
+  // copied the integers it shares with the other before its tied swap)
+  int l[9], r[9];
+#pragma unroll
+  for (int p = 0; p < 9; p++) {
+    const auto sw = __builtin_amdgcn_permlane32_swap((int)acc2[p].x, (int)acc2[p].y, false, false);
+    l[p] = (int)sw[0];
+    r[p] = (int)sw[1];
+  }
+  // (the mono pack as an asm statement: written like the stereo one, the
+  // compiler merges the two branches into one pack behind a copy of L or R
+  // per slot pair -- 18 v_mov_b32 on the stereo path)
+  if (nch == 2) {
+#pragma unroll
+    for (int p = 0; p < 9; p++) {
+      const s2 lr = __builtin_bit_cast(s2, __builtin_amdgcn_cvt_pk_i16(l[p], r[p]));
+      pk[p] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(lr, (s2){-32767, -32767}));
+    }
+  } else {
+#pragma unroll
+    for (int p = 0; p < 9; p++) {
+      s2 ll;
+      asm("v_cvt_pk_i16_i32 %0, %1, %1" : "=v"(ll) : "v"(l[p]));
+      pk[p] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(ll, (s2){-32767, -32767}));
+    }
+  }
+}
+
 // PCM of granule g: one dword per lane and slot pair, non-temporal (c2
 // -1.9 %, c3 -0.8 %).  Issued for replayed granules too, through a resource
 // with no records (straight-line vmcnt accounting).
