@@ -20,7 +20,7 @@ __all__ = ["CHANNEL_DTYPE", "GRANULE_DTYPE", "STREAM_DTYPE", "STATE_DTYPE", "MOD
            "HUFF_STAGE_WIDE", "HUFF_STAGE_MID", "huffman_stage_flags", "decode_streams",
            "WINDOW_DTYPE", "WINDOW_ROW_DTYPE", "WINDOW_GAPLESS", "scan_windows", "WindowPlan",
            "decode_windows_tensor", "RESAMPLE_ROW_DTYPE", "RESAMPLE_FAST", "RESAMPLE_BEST", "Resampler",
-           "stream_rates", "decode_windows_resampled_tensor"]
+           "stream_rates", "decode_windows_resampled_tensor", "VARRESAMPLE_ROW_DTYPE", "VarResampler"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -151,6 +151,14 @@ def lib():
             L.mp3g_resample_host.argtypes = [vp, vp, u64, u64, u64, u64, vp]
             L.mp3g_resample_rows.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp]
             L.mp3g_stream_rates.argtypes = [u32, vp, vp, C.c_int, vp, vp]
+        if hasattr(L, "mp3g_varresampler_create"):  # (an older build through MP3G_LIB: A/B runs)
+            L.mp3g_varresampler_create.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(vp)]
+            L.mp3g_varresampler_free.argtypes = [vp]
+            L.mp3g_varresampler_free.restype = None
+            L.mp3g_varresampler_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(vp),
+                                                 C.POINTER(u32), C.POINTER(u32)]
+            L.mp3g_varresample_host.argtypes = [vp, vp, u64, u64, u64, u64, vp, u32, u32, C.c_float]
+            L.mp3g_varresample_rows.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp]
         if hasattr(L, "mp3g_logmel_create"):  # (an older build through MP3G_LIB: A/B runs)
             L.mp3g_logmel_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, u32,
                                              C.POINTER(vp)]
@@ -814,6 +822,149 @@ class Resampler:
             pass
 
 
+# ---- variable-ratio resampling of decoded rows (include/mp3g.h) -------------
+# one row of VarResampler.rows (mp3g_varresample_row)
+VARRESAMPLE_ROW_DTYPE = np.dtype([("out_start", "<u8"), ("src_origin", "<u8"), ("src_row", "<u4"), ("out_row", "<u4"),
+                                  ("n_src", "<u4"), ("n_out", "<u4"), ("num", "<u4"), ("den", "<u4"),
+                                  ("gain", "<f4"), ("reserved", "<u4")])
+assert VARRESAMPLE_ROW_DTYPE.itemsize == 48
+
+
+class VarResampler:
+    """Windowed-sinc resampler whose ratio num / den (source samples per
+    output sample) and gain belong to the row, not the object
+    (mp3g_varresampler_*): speed and volume perturbation.  One prototype table
+    of (F, D) pairs at 2^precision entries per zero crossing; y[n] is ONE
+    float32 FMA chain over the row's taps in ascending source order, so the
+    device call (rows, one launch whatever the ratios) equals the host
+    reference (host) bit for bit.  device=None (or -1) makes a host-only
+    object."""
+
+    def __init__(self, zeros=RESAMPLE_FAST[0], rolloff=RESAMPLE_FAST[1], beta=RESAMPLE_FAST[2], precision=9,
+                 device=None):
+        self._h = C.c_void_p()
+        self.device = -1 if device is None else int(device)
+        _check(lib().mp3g_varresampler_create(self.device, int(zeros), float(rolloff), float(beta), int(precision),
+                                              C.byref(self._h)))
+        a, b, c, t, g, p = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_void_p()
+        _check(lib().mp3g_varresampler_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(p), C.byref(t),
+                                            C.byref(g)))
+        self.zeros, self.P, self.Z, self.R, self.tile, self.stage = int(zeros), a.value, b.value, c.value, t.value, g.value
+        # a view of the library's table [Z + 1, 2] of (F, D): valid while this object lives
+        self.table = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(2 * (self.Z + 1),)).reshape(-1, 2)
+        self._keep = None
+
+    @staticmethod
+    def ratio(fi, fo, speed=1):
+        """Reduced (num, den) with num / den = speed fi / fo.  speed: an int, a
+        Fraction, a (p, q) pair, or a float taken through
+        Fraction(speed).limit_denominator(10000)."""
+        from fractions import Fraction
+        if isinstance(speed, tuple):
+            sp = Fraction(int(speed[0]), int(speed[1]))
+        elif isinstance(speed, (int, Fraction, np.integer)):
+            sp = Fraction(speed)
+        else:
+            sp = Fraction(float(speed)).limit_denominator(10000)
+        if sp <= 0 or int(fi) <= 0 or int(fo) <= 0:
+            raise Mp3gError(1, "speed and rates must be positive")
+        f = sp * Fraction(int(fi), int(fo))
+        if f.numerator >= 1 << 31 or f.denominator >= 1 << 31:
+            raise Mp3gError(1, "ratio beyond 2^31")
+        return f.numerator, f.denominator
+
+    def step(self, num, den):
+        """The row's table step I (cutoff c = I / 2^P): R, or floor(R den / num)."""
+        return self.R if num <= den else self.R * int(den) // int(num)
+
+    def half_width(self, num, den):
+        """Wr = ceil(Z / I): the row's half width in source samples (0: a copy)."""
+        if num == den:
+            return 0
+        i = self.step(num, den)
+        if i == 0:
+            raise Mp3gError(1, "ratio beyond the table's resolution")
+        return -(-self.Z // i)
+
+    @staticmethod
+    def out_len(n_src, num, den):
+        """Samples of the resampled signal of n_src source samples: ceil(n den / num)."""
+        return -((-int(n_src) * int(den)) // int(num))
+
+    def src_window(self, out_start, n_out, num, den):
+        """The source samples [a, b) the outputs [out_start, out_start + n_out)
+        read (a >= 0), n_out >= 1."""
+        s, T, w = int(out_start), int(n_out), self.half_width(num, den)
+        if w == 0:
+            return s, s + T
+        return max(0, s * num // den - w + 1), (s + T - 1) * num // den + w + 1
+
+    def host(self, src, src_origin, out_start, n_out, num, den, gain=1.0):
+        """The reference on the CPU (mp3g_varresample_host): outputs [out_start,
+        out_start + n_out) of the signal whose samples [src_origin, src_origin
+        + len(src)) are `src` (float32) and zero elsewhere, at num / den source
+        samples per output, times gain."""
+        src = np.ascontiguousarray(src, dtype=np.float32)
+        out = np.zeros(int(n_out), np.float32)
+        if not (0 <= int(num) < 1 << 32 and 0 <= int(den) < 1 << 32):
+            raise Mp3gError(1, "num and den in [1, 2^31)")
+        _check(lib().mp3g_varresample_host(self._h, _ptr(src) if len(src) else None, int(src_origin), len(src),
+                                           int(out_start), int(n_out), _ptr(out) if n_out else None, int(num),
+                                           int(den), float(gain)))
+        return out
+
+    def rows(self, d_src, d_out, rows, stream=None):
+        """The device call (mp3g_varresample_rows): tensors as Resampler.rows;
+        rows: VARRESAMPLE_ROW_DTYPE[n] (numpy: checked -- a row outside the
+        tensors, with num or den outside [1, 2^31) or with a ratio beyond the
+        table's resolution is refused -- uploaded and kept until the next
+        call; or a uint8 device tensor of n * 48 bytes, taken as it is).  ONE
+        launch for all rows.  Asynchronous on `stream` (a hipStream_t; None =
+        the current torch stream)."""
+        import torch
+        for t in (d_src, d_out):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() not in (2, 3) or not t.is_cuda:
+                raise ValueError("VarResampler.rows: contiguous float32 device tensors [*, C, S] or [*, S]")
+        nch = d_out.shape[1] if d_out.dim() == 3 else 1
+        if (d_src.shape[1] if d_src.dim() == 3 else 1) != nch:
+            raise ValueError("VarResampler.rows: source and output differ in channels")
+        if isinstance(rows, np.ndarray):
+            rows = np.ascontiguousarray(rows, dtype=VARRESAMPLE_ROW_DTYPE)
+            n = len(rows)
+            if n and (int(rows["src_row"].max()) >= d_src.shape[0] or int(rows["out_row"].max()) >= d_out.shape[0]
+                      or int(rows["n_src"].max()) > d_src.shape[-1] or int(rows["n_out"].max()) > d_out.shape[-1]):
+                raise ValueError("VarResampler.rows: a row lies outside the tensors")
+            if n:
+                num, den = rows["num"].astype(np.uint64), rows["den"].astype(np.uint64)
+                if (int(num.min()) < 1 or int(den.min()) < 1 or int(num.max()) >= 1 << 31 or int(den.max()) >= 1 << 31
+                        or bool((num > np.uint64(self.R) * den).any())):
+                    raise Mp3gError(1, "VarResampler.rows: num or den outside [1, 2^31), or a ratio beyond the "
+                                       "table's resolution")
+            d_rows = torch.from_numpy(rows.view(np.uint8).copy()).to(d_out.device) if n else None
+        else:
+            d_rows, n = rows, rows.numel() // VARRESAMPLE_ROW_DTYPE.itemsize
+        self._keep = d_rows
+        if stream is None:
+            stream = torch.cuda.current_stream(d_out.device).cuda_stream
+        _check(lib().mp3g_varresample_rows(self._h, C.c_void_p(d_src.data_ptr()), int(d_src.shape[-1]),
+                                           C.c_void_p(d_out.data_ptr()), int(d_out.shape[-1]), int(nch),
+                                           C.c_void_p(d_rows.data_ptr()) if n else None, n,
+                                           C.c_void_p(stream) if stream else None))
+        return d_rows
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.table = None
+            lib().mp3g_varresampler_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def stream_rates(datas, n_threads=0, channels=False):
     """The sample rate of each stream's first valid frame (mp3g_stream_rates; 0:
     no valid frame) as int32[B]; channels=True: (rates, channel counts)."""
@@ -825,7 +976,7 @@ def stream_rates(datas, n_threads=0, channels=False):
 
 
 def decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=MODE_EXACT, out_format=OUT_F32_PLANAR,
-                                    gapless=False, quality="fast", n_threads=0, device=0):
+                                    gapless=False, quality="fast", n_threads=0, device=0, speed=None, gain=None):
     """decode_windows_tensor at ONE sample rate: starts[k] and n_samples count
     samples at `rate`, and row k holds y_k[starts[k], starts[k] + lengths[k]),
     zero-padded to n_samples, where y_k is the resample (Resampler, preset
@@ -843,7 +994,18 @@ def decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=MODE_EX
     Returns (batch, lengths, end_status, rates): batch [B, 2, n_samples]
     (OUT_F32_PLANAR) or [B, n_samples] (OUT_F32_MONO) on cuda:device, lengths
     int64[B], end_status of the windowed scan, rates int32[B] (0: no valid
-    frame, an all-zero row)."""
+    frame, an all-zero row).
+
+    speed, gain: speed and volume perturbation, one entry per stream each
+    (speed as VarResampler.ratio takes it; None for either: 1 for every
+    stream).  With both None this is the polyphase path above.  Otherwise
+    stream k is played speed[k] times faster -- num / den = speed[k] fi / rate
+    source samples per output sample -- and scaled by gain[k]; starts and
+    n_samples count samples of the perturbed signal, lengths[k] = ceil(N_k den
+    / num) - starts[k] clamped to [0, n_samples], and every row goes through
+    ONE VarResampler.rows launch behind the windowed decode: every sample
+    equals VarResampler.host on the same slice of the full decode bit for
+    bit."""
     import torch
     _check_window_format(out_format)
     if int(rate) <= 0:
@@ -853,6 +1015,9 @@ def decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=MODE_EX
     starts = [int(s) for s in starts]
     if len(starts) != B or T < 0 or any(s < 0 for s in starts):
         raise ValueError("decode_windows_resampled_tensor: one start >= 0 per stream")
+    if speed is not None or gain is not None:
+        return _decode_windows_perturbed(datas, starts, T, int(rate), mode, out_format, gapless,
+                                         (zeros, rolloff, beta), n_threads, device, speed, gain)
     rates = stream_rates(datas, n_threads=n_threads)
     rs = {int(f): Resampler(int(f), int(rate), zeros, rolloff, beta, device=device) for f in set(rates.tolist()) if f}
     dev = torch.device("cuda", device)
@@ -891,6 +1056,60 @@ def decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=MODE_EX
                  mode, device, then=resample)
     for r in rs.values():
         r.close()
+    return batch, lengths, s["end_status"], rates
+
+
+def _decode_windows_perturbed(datas, starts, T, rate, mode, out_format, gapless, quality, n_threads, device, speed,
+                              gain):
+    """decode_windows_resampled_tensor with a speed and a gain per stream: the
+    windowed decode of each stream's source window, then one VarResampler.rows
+    launch for all rows."""
+    import torch
+    B = len(datas)
+    speed = [1] * B if speed is None else list(speed)
+    gain = [1.0] * B if gain is None else [float(g) for g in gain]
+    if len(speed) != B or len(gain) != B:
+        raise ValueError("decode_windows_resampled_tensor: one speed and one gain per stream")
+    rates = stream_rates(datas, n_threads=n_threads)
+    vr = VarResampler(*quality, device=device)
+    try:
+        dev = torch.device("cuda", device)
+        planar = out_format == OUT_F32_PLANAR
+        batch = torch.zeros((B, 2, T) if planar else (B, T), dtype=torch.float32, device=dev)
+        lengths = np.zeros(B, np.int64)
+        ratio = [vr.ratio(int(rates[k]), rate, speed[k]) if rates[k] else (1, 1) for k in range(B)]
+        # each stream's source window [src0, src0 + src_n) (none: no valid frame)
+        src0, src_n = np.zeros(B, np.uint64), np.zeros(B, np.uint64)
+        for k in range(B):
+            if rates[k] and T:
+                a, b = vr.src_window(starts[k], T, *ratio[k])
+                if b - a > (1 << 26):
+                    raise Mp3gError(1, "source window of more than MP3G_WINDOW_MAX_SAMPLES samples")
+                src0[k], src_n[k] = a, b - a
+        s = _scan_windows(datas, src0, src_n, gapless, n_threads)
+        T_src = int(src_n.max()) if B else 0
+        inter = (torch.zeros((B, 2, T_src) if planar else (B, T_src), dtype=torch.float32, device=dev)
+                 if len(s["granules"]) else None)
+
+        def resample(st):  # one launch for every row, behind the windowed decode
+            n_valid = s["rows"]["n_valid"].astype(np.int64)
+            ks = [k for k in range(B) if rates[k] and n_valid[k] > 0]
+            rows = np.zeros(len(ks), VARRESAMPLE_ROW_DTYPE)
+            for i, k in enumerate(ks):
+                a, want = int(src0[k]), int(src_n[k])
+                # fewer samples than asked for: the stream ends at N = a + n_valid
+                ln = T if n_valid[k] >= want else min(T, max(0, vr.out_len(a + int(n_valid[k]), *ratio[k])
+                                                             - starts[k]))
+                lengths[k] = ln
+                rows[i] = (starts[k], a, k, k, int(n_valid[k]), ln, ratio[k][0], ratio[k][1], gain[k], 0)
+            rows = rows[rows["n_out"] > 0]
+            if len(rows):
+                vr.rows(inter, batch, rows, stream=st.cuda_stream)
+
+        _decode_scan(s, lambda: WindowPlan(s["streams"], s["rows"], T_src, mode=mode, device=device), inter,
+                     out_format, mode, device, then=resample)
+    finally:
+        vr.close()
     return batch, lengths, s["end_status"], rates
 
 
@@ -996,7 +1215,8 @@ class LogMel:
 
 def decode_windows_logmel_tensor(datas, starts, n_samples, rate=16000, n_fft=400, hop=160, n_mels=80, clamp=True,
                                  center=True, fmin=0.0, fmax=0.0, n_frames=None, mode=MODE_EXACT,
-                                 out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0, device=0):
+                                 out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0, device=0,
+                                 speed=None, gain=None):
     """decode_windows_resampled_tensor followed by LogMel.execute on the same
     torch stream: the log-mel features of each stream's window [starts[k],
     starts[k] + n_samples) at `rate`, zero padding included.  F = n_frames, by
@@ -1007,7 +1227,11 @@ def decode_windows_logmel_tensor(datas, starts, n_samples, rate=16000, n_fft=400
     F] (OUT_F32_MONO) or [B, 2, n_mels, F] (OUT_F32_PLANAR) on cuda:device,
     equal to LogMel.host on the rows of decode_windows_resampled_tensor bit for
     bit; frame_lengths int64[B] = min(F, ceil(lengths / hop)), the frames that
-    start inside each stream's valid samples."""
+    start inside each stream's valid samples.
+
+    speed, gain: speed and volume perturbation before everything else, one
+    entry per stream each (decode_windows_resampled_tensor); starts and
+    n_samples then count samples of the perturbed signal."""
     import torch
     lm = LogMel(rate, n_fft, hop, n_mels, fmin, fmax, center=center, clamp=clamp, device=device)
     try:
@@ -1018,7 +1242,7 @@ def decode_windows_logmel_tensor(datas, starts, n_samples, rate=16000, n_fft=400
             raise Mp3gError(1, "more frames than a row of n_samples has")
         batch, lengths, end_status, rates = decode_windows_resampled_tensor(
             datas, starts, T, rate, mode=mode, out_format=out_format, gapless=gapless, quality=quality,
-            n_threads=n_threads, device=device)
+            n_threads=n_threads, device=device, speed=speed, gain=gain)
         feats = lm.execute(batch, n_frames=F)
         torch.cuda.current_stream(feats.device).synchronize()
     finally:
@@ -1139,7 +1363,8 @@ class FBank:
 def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_length_ms=25.0, frame_shift_ms=10.0,
                                 n_mels=80, low_freq=20.0, high_freq=0.0, preemphasis=0.97, remove_dc=True,
                                 window="povey", snip_edges=True, scale=32768.0, n_frames=None, mode=MODE_EXACT,
-                                out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0, device=0):
+                                out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0, device=0,
+                                speed=None, gain=None):
     """decode_windows_resampled_tensor followed by FBank.execute on the same
     torch stream: Kaldi's filter-bank features of each stream's window
     [starts[k], starts[k] + n_samples) at `rate`, zero padding included.
@@ -1151,7 +1376,11 @@ def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_leng
     bit; frame_lengths int64[B], the frames that lie wholly inside each stream's
     valid samples: clamp((len - N) // hop + 1, 0, F) with snip_edges, else
     min(F, (len + hop // 2) // hop).  A frameless stream's rows are all
-    logf(2^-23)."""
+    logf(2^-23).
+
+    speed, gain: speed and volume perturbation before everything else, one
+    entry per stream each (decode_windows_resampled_tensor); starts and
+    n_samples then count samples of the perturbed signal."""
     import torch
     fb = FBank(rate, frame_length_ms, frame_shift_ms, n_mels, low_freq, high_freq, preemphasis, remove_dc, window,
                snip_edges, scale, device=device)
@@ -1163,7 +1392,7 @@ def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_leng
             raise Mp3gError(1, "more frames than a row of n_samples has")
         batch, lengths, end_status, rates = decode_windows_resampled_tensor(
             datas, starts, T, rate, mode=mode, out_format=out_format, gapless=gapless, quality=quality,
-            n_threads=n_threads, device=device)
+            n_threads=n_threads, device=device, speed=speed, gain=gain)
         feats = torch.empty(tuple(batch.shape[:-1]) + (F, fb.n_mels), dtype=torch.float32, device=batch.device)
         fb.execute(batch, feats)
         torch.cuda.current_stream(feats.device).synchronize()
@@ -1537,7 +1766,8 @@ def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_lengt
                                energy_floor=0.0, low_freq=20.0, high_freq=0.0, preemphasis=0.97, remove_dc=True,
                                window="povey", snip_edges=True, scale=32768.0, cmvn=None, n_frames=None,
                                mode=MODE_EXACT, out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0,
-                               device=0, cmn_window=300, min_cmn_window=100, center=True, vad=None):
+                               device=0, cmn_window=300, min_cmn_window=100, center=True, vad=None,
+                               speed=None, gain=None):
     """decode_windows_resampled_tensor, MFCC.execute and, with cmvn = "mean"
     or "mean_var", the per-row normalisation over each stream's own frames, all
     on the current torch stream: Kaldi's MFCC features of each stream's window
@@ -1559,7 +1789,11 @@ def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_lengt
     features' coefficient 0 (use_energy is required), the normalisation of
     whichever kind runs over all of a stream's frames, the selection comes last
     (select_frames; the frames after the voiced ones are zeros).  frame_lengths
-    are then the voiced counts, int64 [B] or, planar, [B, 2]."""
+    are then the voiced counts, int64 [B] or, planar, [B, 2].
+
+    speed, gain: speed and volume perturbation before everything else, one
+    entry per stream each (decode_windows_resampled_tensor); starts and
+    n_samples then count samples of the perturbed signal."""
     import torch
     if cmvn not in CMVN_MODES and cmvn not in SLIDING_CMVN_MODES:
         raise Mp3gError(1, "decode_windows_mfcc_tensor: cmvn is None, 'mean', 'mean_var', 'sliding' or 'sliding_var'")
@@ -1578,7 +1812,7 @@ def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_lengt
             raise Mp3gError(1, "more frames than a row of n_samples has")
         batch, lengths, end_status, rates = decode_windows_resampled_tensor(
             datas, starts, T, rate, mode=mode, out_format=out_format, gapless=gapless, quality=quality,
-            n_threads=n_threads, device=device)
+            n_threads=n_threads, device=device, speed=speed, gain=gain)
         feats = torch.empty(tuple(batch.shape[:-1]) + (F, mf.n_ceps), dtype=torch.float32, device=batch.device)
         mf.execute(batch, feats)
         if snip_edges:
@@ -1970,7 +2204,7 @@ def true_peak(d_x, lengths=None, rows=None, stream=None, d_out=None):
 
 def decode_windows_normalized_tensor(datas, starts, n_samples, target_lufs=-23.0, peak_ceiling=None, rate=None,
                                      mode=MODE_EXACT, out_format=OUT_F32_PLANAR, gapless=False, quality="fast",
-                                     n_threads=0, device=0, peak="sample", extended=False):
+                                     n_threads=0, device=0, peak="sample", extended=False, speed=None, gain=None):
     """A windowed decode, its loudness and the gain to target_lufs, all on the
     GPU.  rate=None: decode_windows_tensor, each row measured at its stream's
     own rate (stream_rates; one Loudness and one measurement per distinct
@@ -1993,18 +2227,25 @@ def decode_windows_normalized_tensor(datas, starts, n_samples, target_lufs=-23.0
     Returns what the underlying call returns -- (batch, lengths, end_status)
     or (batch, lengths, end_status, rates) -- followed by stats
     (LOUDNESS_STATS_DTYPE[B], numpy: Loudness.host of the un-normalised batch
-    byte for byte) and gains (float32[B], numpy; ones when only measuring)."""
+    byte for byte) and gains (float32[B], numpy; ones when only measuring).
+
+    speed, gain: speed and volume perturbation before everything else, one
+    entry per stream each (decode_windows_resampled_tensor); starts and
+    n_samples then count samples of the perturbed signal."""
     import torch
     if peak not in ("sample", "true"):
         raise ValueError("decode_windows_normalized_tensor: peak is 'sample' or 'true'")
     B = len(datas)
+    if rate is None and (speed is not None or gain is not None):
+        raise Mp3gError(1, "decode_windows_normalized_tensor: speed and gain need a rate")
     if rate is None:
         res = decode_windows_tensor(datas, starts, n_samples, mode=mode, out_format=out_format, gapless=gapless,
                                     n_threads=n_threads, device=device)
         row_rates = stream_rates(datas, n_threads=n_threads)
     else:
         res = decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=mode, out_format=out_format,
-                                              gapless=gapless, quality=quality, n_threads=n_threads, device=device)
+                                              gapless=gapless, quality=quality, n_threads=n_threads, device=device,
+                                              speed=speed, gain=gain)
         row_rates = np.where(res[3] > 0, int(rate), 0)
     batch, lengths = res[0], res[1]
     # a row no Loudness measures keeps this record: the zero row's
@@ -2350,19 +2591,25 @@ def augment(d_x, lengths=None, reverb=None, rir_index=None, noise=None, noise_le
 
 
 def decode_windows_augmented_tensor(datas, starts, n_samples, rate, mode=MODE_EXACT, out_format=OUT_F32_PLANAR,
-                                    gapless=False, quality="fast", n_threads=0, device=0, **augment_keywords):
+                                    gapless=False, quality="fast", n_threads=0, device=0, speed=None, gain=None,
+                                    **augment_keywords):
     """decode_windows_resampled_tensor, then augment on its batch and lengths
     with the keywords of augment (reverb, rir_index, noise, noise_lengths,
     noise_power, additive, normalize, out, stats, stream): the augmented
     training batch at one sample rate with no copy to the host; it equals
     augment_host of the resampled tensor bit for bit.  Returns (out, lengths,
     end_status, rates, stats).  Without any augment keyword it is
-    decode_windows_resampled_tensor, and returns what that returns."""
+    decode_windows_resampled_tensor, and returns what that returns.
+
+    speed, gain: speed and volume perturbation before everything else, one
+    entry per stream each (decode_windows_resampled_tensor); starts and
+    n_samples then count samples of the perturbed signal."""
     unknown = set(augment_keywords) - set(_AUGMENT_KEYS)
     if unknown:
         raise TypeError("decode_windows_augmented_tensor: unknown keyword " + sorted(unknown)[0])
     res = decode_windows_resampled_tensor(datas, starts, n_samples, rate, mode=mode, out_format=out_format,
-                                          gapless=gapless, quality=quality, n_threads=n_threads, device=device)
+                                          gapless=gapless, quality=quality, n_threads=n_threads, device=device,
+                                          speed=speed, gain=gain)
     if not augment_keywords:
         return res
     out, stats = augment(res[0], res[1], **augment_keywords)
@@ -2481,7 +2728,7 @@ class STFT:
 def decode_windows_stft_tensor(datas, starts, n_samples, rate, n_fft=2048, hop=512, win_length=None, output="power",
                                n_mels=0, fmin=0.0, fmax=0.0, htk=False, norm=True, log=None, floor=None, center=True,
                                n_frames=None, mode=MODE_EXACT, out_format=OUT_F32_MONO, gapless=False, quality="fast",
-                               n_threads=0, device=0):
+                               n_threads=0, device=0, speed=None, gain=None):
     """decode_windows_resampled_tensor followed by one STFT.execute on the same
     torch stream: the spectrogram (or mel spectrogram) of each stream's window
     [starts[k], starts[k] + n_samples) at `rate`, zero padding included.  F =
@@ -2493,7 +2740,11 @@ def decode_windows_stft_tensor(datas, starts, n_samples, rate, n_fft=2048, hop=5
     or, for output="complex", complex64; equal to STFT.host on the rows of
     decode_windows_resampled_tensor bit for bit; frame_lengths int64[B] = min(F,
     ceil(lengths / hop)), the frames that start inside each stream's valid
-    samples."""
+    samples.
+
+    speed, gain: speed and volume perturbation before everything else, one
+    entry per stream each (decode_windows_resampled_tensor); starts and
+    n_samples then count samples of the perturbed signal."""
     import torch
     st = STFT(rate, n_fft, hop, win_length, output, n_mels, fmin, fmax, htk, norm, log, floor, center, device=device)
     try:
@@ -2504,7 +2755,7 @@ def decode_windows_stft_tensor(datas, starts, n_samples, rate, n_fft=2048, hop=5
             raise Mp3gError(1, "more frames than a row of n_samples has")
         batch, lengths, end_status, rates = decode_windows_resampled_tensor(
             datas, starts, T, rate, mode=mode, out_format=out_format, gapless=gapless, quality=quality,
-            n_threads=n_threads, device=device)
+            n_threads=n_threads, device=device, speed=speed, gain=gain)
         feats = st.execute(batch, n_frames=F)
         torch.cuda.current_stream(feats.device).synchronize()
     finally:

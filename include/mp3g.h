@@ -64,7 +64,9 @@ extern "C" {
  *    mp3g_true_peak_*, mp3g_loudness_range_*, mp3g_gain_rows_peak and
  *    mp3g_gain_host_peak; sliding-window CMN, energy VAD and voiced-frame
  *    selection of feature tensors -- mp3g_sliding_cmn_*, mp3g_vad_energy_* and
- *    mp3g_select_frames_*.) */
+ *    mp3g_select_frames_*; variable-ratio resampling of decoded rows (speed
+ *    and volume perturbation) -- mp3g_varresampler_*, mp3g_varresample_host
+ *    and mp3g_varresample_rows.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -628,6 +630,90 @@ int mp3g_resample_rows(const mp3g_resampler* r, const float* d_src, uint32_t src
  * stream without a valid frame gets 0 and 0. */
 int mp3g_stream_rates(uint32_t n_streams, const uint8_t* const* datas, const size_t* lens, int n_threads,
                       int* rates, int* channels);
+
+/* ---- variable-ratio resampling of decoded rows ------------------------------
+ * Speed and volume perturbation (sox `speed`, Kaldi's 3-way speed and volume
+ * recipes, a factor drawn per utterance): a resampler whose ratio and gain are
+ * fields of the row descriptor, so ONE launch serves rows of any ratios.  No
+ * reference counterpart (go-mp3 delivers every stream at its own rate).
+ *
+ * Object.  One prototype table that depends on no ratio: P = precision (5..9),
+ * Z = zeros << P and, for i = 0..Z,
+ *   f(v) = sinc(v) kaiser(v / zeros),  F[i] = f(i / 2^P),  F[Z] = 0,
+ *   D[i] = f((i + 1) / 2^P) - f(i / 2^P),  D[Z] = 0
+ * (sinc, kaiser and I0 as in the section above), computed in float64 and
+ * rounded once to float32; R = floor(rolloff 2^P) is fixed at creation.  zeros
+ * outside 1..64 or precision outside 5..9 is MP3G_ERR_UNSUPPORTED, a rolloff
+ * outside (0, 1] or R == 0 MP3G_ERR_INVALID_ARGUMENT, before any device call.
+ * The presets are the MP3G_RESAMPLE_FAST_* / _BEST_* triples.
+ *
+ * Row.  num / den is source samples per output sample, 1 <= num, den < 2^31
+ * (not necessarily reduced); gain multiplies the output.
+ *
+ * Cutoff, in integers only: I = R for num <= den, else floor(R den / num) (64
+ * bits); c = I / 2^P (exact in float32); Wr = ceil(Z / I) is the row's half
+ * width in source samples.  The quantised cutoff is at most 2^-P below
+ * rolloff min(1, den / num): the price of an interpolation fraction that is
+ * constant along a wing (resampy's resample_f loop, with its truncated
+ * index_step made consistent between the filter's scale and its gain).
+ *
+ * Signal.  x is zero outside [0, N).  For output n, (q, r) = divmod(n num, den)
+ * (64-bit; n num / den < 2^62).
+ *   left wing:  source j = q - k, k >= 0, table index iL(k) = oL + I k with
+ *     (oL, remL) = divmod(I r, den), etaL = (float)((double)remL / (double)den)
+ *   right wing: source j = q + 1 + k, index iR(k) = oR + I k with
+ *     (oR, remR) = divmod(I (den - r), den), etaR likewise
+ * A tap exists while its index is < Z; its weight is w = fmaf(eta, D[i], F[i]).
+ *   acc = +0.0f;  acc = fmaf(w, x[j], acc) over all existing taps in ASCENDING j
+ *   (the left wing from its farthest tap inwards, then the right wing outwards)
+ *   y[n] = (c * acc) * gain      -- two float32 multiplications, in that order
+ * Taps on samples outside [0, N) are skipped.  The order is part of the
+ * contract: the device call equals mp3g_varresample_host bit for bit, whatever
+ * the tiling.  y has ceil(N den / num) samples.  num == den is a copy times
+ * gain: y[n] = x[n] * gain, no filter (-0 stays -0 at gain = 1). */
+typedef struct mp3g_varresampler mp3g_varresampler;
+/* Builds the table; device >= 0 also uploads it to that device (once), device
+ * = -1 makes a host-only object (mp3g_varresample_host, mp3g_varresampler_info). */
+int mp3g_varresampler_create(int device, int zeros, double rolloff, double beta, int precision,
+                             mp3g_varresampler** out);
+void mp3g_varresampler_free(mp3g_varresampler* r);
+/* P, Z, R, the host table float [Z + 1][2] of (F[i], D[i]) pairs (owned by the
+ * object), the device call's output tile length, and the floats of its source
+ * stage -- a tile's span of (tile - 1) num / den + 2 Wr samples is staged when
+ * it is at most stage / n_channels (any may be NULL). */
+int mp3g_varresampler_info(const mp3g_varresampler* r, uint32_t* precision, uint32_t* Z, uint32_t* R,
+                           const float** table, uint32_t* tile, uint32_t* stage);
+/* The definition above in plain C++ for one row (the reference the device call
+ * equals): source sample j is src[j - src_origin] for src_origin <= j <
+ * src_origin + n_src and 0 otherwise; writes y[out_start .. out_start + n_out)
+ * to `out`.  num or den outside [1, 2^31), or a ratio with I == 0 (num > R den),
+ * is MP3G_ERR_INVALID_ARGUMENT. */
+int mp3g_varresample_host(const mp3g_varresampler* r, const float* src, uint64_t src_origin, uint64_t n_src,
+                          uint64_t out_start, uint64_t n_out, float* out, uint32_t num, uint32_t den, float gain);
+/* One row of the device call: mp3g_resample_row's fields, the ratio and the
+ * gain.  48 bytes. */
+typedef struct mp3g_varresample_row {
+  uint64_t out_start;
+  uint64_t src_origin;
+  uint32_t src_row;
+  uint32_t out_row;
+  uint32_t n_src; /* <= src_stride */
+  uint32_t n_out; /* <= out_stride */
+  uint32_t num;   /* source samples per output sample: num / den */
+  uint32_t den;
+  float gain;
+  uint32_t reserved; /* 0 */
+} mp3g_varresample_row;
+/* Buffers as mp3g_resample_rows.  ONE launch for all rows, whatever their
+ * ratios; its shape depends on n_rows, out_stride and n_channels alone:
+ * asynchronous on hip_stream and graph-capturable.  Writes the n_out samples
+ * of each row and plane and nothing else (n_out is cut at out_stride, n_src at
+ * src_stride); the kernel stays within the strides for any descriptor
+ * contents, and a row with den == 0, num == 0 or I == 0 gets +0 in its n_out
+ * samples.  Strides and n_rows are below 2^31. */
+int mp3g_varresample_rows(const mp3g_varresampler* r, const float* d_src, uint32_t src_stride, float* d_out,
+                          uint32_t out_stride, uint32_t n_channels, const mp3g_varresample_row* d_rows,
+                          uint32_t n_rows, void* hip_stream);
 
 /* ---- log-mel features of decoded rows ---------------------------------------
  * The input of a speech model from the float rows of the windowed, resampled
