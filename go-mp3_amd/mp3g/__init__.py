@@ -212,6 +212,9 @@ def lib():
             L.mp3g_vad_energy_host.argtypes = [vp, u32, u32, u32, u32, u32, u32, vp, f32, f32, f32, u32, vp, vp]
             L.mp3g_select_frames_rows.argtypes = [C.c_int, vp, u32, u32, u32, u32, u32, vp, vp, vp, u32, u32, vp, vp]
             L.mp3g_select_frames_host.argtypes = [vp, u32, u32, u32, u32, u32, vp, vp, vp, u32, u32, vp]
+        if hasattr(L, "mp3g_specaug_rows"):
+            L.mp3g_specaug_rows.argtypes = [C.c_int, vp, vp, u32, u32, u32, u32, u32, vp, vp, u32, C.c_float, vp, vp]
+            L.mp3g_specaug_host.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, vp, u32, C.c_float, vp]
         if hasattr(L, "mp3g_loudness_create"):
             dp = C.POINTER(vp)
             L.mp3g_loudness_create.argtypes = [C.c_int, C.c_int, dp]
@@ -1216,7 +1219,7 @@ class LogMel:
 def decode_windows_logmel_tensor(datas, starts, n_samples, rate=16000, n_fft=400, hop=160, n_mels=80, clamp=True,
                                  center=True, fmin=0.0, fmax=0.0, n_frames=None, mode=MODE_EXACT,
                                  out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0, device=0,
-                                 speed=None, gain=None):
+                                 speed=None, gain=None, spec_augment=None):
     """decode_windows_resampled_tensor followed by LogMel.execute on the same
     torch stream: the log-mel features of each stream's window [starts[k],
     starts[k] + n_samples) at `rate`, zero padding included.  F = n_frames, by
@@ -1231,7 +1234,12 @@ def decode_windows_logmel_tensor(datas, starts, n_samples, rate=16000, n_fft=400
 
     speed, gain: speed and volume perturbation before everything else, one
     entry per stream each (decode_windows_resampled_tensor); starts and
-    n_samples then count samples of the perturbed signal."""
+    n_samples then count samples of the perturbed signal.
+
+    spec_augment: None, or SpecAugment of the features in the frequency-major
+    layout (spec_augment with freq_major=True) on the same stream: a
+    descriptor array [B], or a dict of spec_augment_rows' options plus `rng`
+    and `fill`, whose rows are drawn from the returned frame_lengths."""
     import torch
     lm = LogMel(rate, n_fft, hop, n_mels, fmin, fmax, center=center, clamp=clamp, device=device)
     try:
@@ -1244,10 +1252,13 @@ def decode_windows_logmel_tensor(datas, starts, n_samples, rate=16000, n_fft=400
             datas, starts, T, rate, mode=mode, out_format=out_format, gapless=gapless, quality=quality,
             n_threads=n_threads, device=device, speed=speed, gain=gain)
         feats = lm.execute(batch, n_frames=F)
+        flen = np.minimum(F, -(-lengths // lm.hop))
+        if spec_augment is not None:
+            feats = _specaug_after("decode_windows_logmel_tensor", feats, flen, spec_augment, lm.n_mels, True)
         torch.cuda.current_stream(feats.device).synchronize()
     finally:
         lm.close()
-    return feats, np.minimum(F, -(-lengths // lm.hop)), end_status, rates
+    return feats, flen, end_status, rates
 
 
 # ---- Kaldi filter-bank features of decoded rows (include/mp3g.h) -------------
@@ -1364,7 +1375,7 @@ def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_leng
                                 n_mels=80, low_freq=20.0, high_freq=0.0, preemphasis=0.97, remove_dc=True,
                                 window="povey", snip_edges=True, scale=32768.0, n_frames=None, mode=MODE_EXACT,
                                 out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0, device=0,
-                                speed=None, gain=None):
+                                speed=None, gain=None, cmvn=None, spec_augment=None):
     """decode_windows_resampled_tensor followed by FBank.execute on the same
     torch stream: Kaldi's filter-bank features of each stream's window
     [starts[k], starts[k] + n_samples) at `rate`, zero padding included.
@@ -1380,8 +1391,18 @@ def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_leng
 
     speed, gain: speed and volume perturbation before everything else, one
     entry per stream each (decode_windows_resampled_tensor); starts and
-    n_samples then count samples of the perturbed signal."""
+    n_samples then count samples of the perturbed signal.
+
+    cmvn: None, "mean" or "mean_var": the per-row normalisation of
+    decode_windows_mfcc_tensor (cmvn) over each stream's frame_lengths frames,
+    in place on the same stream.  spec_augment: None, or SpecAugment of the
+    (normalised) features (spec_augment, time-major) on the same stream: a
+    descriptor array [B], or a dict of spec_augment_rows' options plus `rng`
+    and `fill`, whose rows are drawn from the returned frame_lengths.  The
+    recipes normalise before they mask: a fill of 0 is then the mean."""
     import torch
+    if cmvn not in CMVN_MODES:
+        raise Mp3gError(1, "decode_windows_fbank_tensor: cmvn is None, 'mean' or 'mean_var'")
     fb = FBank(rate, frame_length_ms, frame_shift_ms, n_mels, low_freq, high_freq, preemphasis, remove_dc, window,
                snip_edges, scale, device=device)
     try:
@@ -1395,11 +1416,15 @@ def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_leng
             n_threads=n_threads, device=device, speed=speed, gain=gain)
         feats = torch.empty(tuple(batch.shape[:-1]) + (F, fb.n_mels), dtype=torch.float32, device=batch.device)
         fb.execute(batch, feats)
-        torch.cuda.current_stream(feats.device).synchronize()
         if snip_edges:
             flen = np.clip((lengths - fb.N) // fb.hop + 1, 0, F)
         else:
             flen = np.minimum(F, (lengths + fb.hop // 2) // fb.hop)
+        if CMVN_MODES[cmvn] is not None:
+            _cmvn_rows(feats, flen, norm_vars=CMVN_MODES[cmvn])
+        if spec_augment is not None:
+            feats = _specaug_after("decode_windows_fbank_tensor", feats, flen, spec_augment, fb.n_mels, False)
+        torch.cuda.current_stream(feats.device).synchronize()
     finally:
         fb.close()
     return feats, flen, end_status, rates
@@ -1759,6 +1784,173 @@ def select_frames(feats, voiced, frame_lengths, n_frames_out=None, n_cols=None, 
                                          int(feats.shape[-1]), cols, _dptr(voiced), _dptr(lengths), _dptr(out),
                                          int(out.shape[-2]), int(out.shape[-1]), _dptr(m), _stream_of(feats, stream)))
     return out, m
+
+
+# ---- SpecAugment: time warp, frequency and time masks (include/mp3g.h) ------------
+SPECAUG_FREQ_MAJOR = 1
+SPECAUG_WARP = 2
+SPECAUG_FILL_MEAN = 4
+SPECAUG_MAX_TIME_MASKS = 16
+SPECAUG_MAX_FREQ_MASKS = 4
+SPECAUG_ROW_DTYPE = np.dtype([("warp_center", "<u4"), ("warp_to", "<u4"), ("n_time", "<u4"), ("n_freq", "<u4"),
+                              ("time", "<u4", (SPECAUG_MAX_TIME_MASKS, 2)),
+                              ("freq", "<u4", (SPECAUG_MAX_FREQ_MASKS, 2))])
+assert SPECAUG_ROW_DTYPE.itemsize == 176
+
+
+def _specaug_flags(name, fill, freq_major, warp):
+    """(flags, fill_value) of a spec_augment call."""
+    flags = (SPECAUG_FREQ_MAJOR if freq_major else 0) | (SPECAUG_WARP if warp else 0)
+    if isinstance(fill, str):
+        if fill != "mean":
+            raise ValueError(name + ": fill is a number or 'mean'")
+        return flags | SPECAUG_FILL_MEAN, 0.0
+    return flags, float(fill)
+
+
+def spec_augment_host(feats, frame_lengths, rows, fill=0.0, freq_major=False, warp=True, n_cols=None):
+    """The reference on the CPU (mp3g_specaug_host): SpecAugment of the float32
+    array feats -- [B, F, S] or [B, C, F, S], or with freq_major [B, bins, S] or
+    [B, C, bins, S] with the frames along the last axis -- as include/mp3g.h
+    states it: per row, from rows[b] (SPECAUG_ROW_DTYPE; spec_augment_rows
+    draws them), first the two-segment cubic time warp (when `warp`), then the
+    union of the row's time and frequency masks written with `fill`, a number or
+    "mean" (the mean of the row's live input per plane, in float64).  Only the
+    row's first min(frame_lengths[b], F) frames are warped and masked; later
+    frames are copied.  n_cols: the live count of the last axis (bins in
+    time-major, frames in frequency-major; all S by default); words past it keep
+    feats' values.  Returns out, or (out, fills float32 [B, (C)]) with "mean"."""
+    x, B, planes, lengths, live = _host_feats("spec_augment_host", feats, frame_lengths, n_cols)
+    desc = np.ascontiguousarray(rows, dtype=SPECAUG_ROW_DTYPE)
+    if desc.shape != (B,):
+        raise ValueError("spec_augment_host: one descriptor per row")
+    flags, value = _specaug_flags("spec_augment_host", fill, freq_major, warp)
+    n_frames, n_bins = (live, x.shape[-2]) if freq_major else (x.shape[-2], live)
+    out = x.copy()
+    fills = np.zeros(x.shape[:-2], np.float32)
+    _check(lib().mp3g_specaug_host(_ptr(x) if x.size else None, _ptr(out) if out.size else None, B, planes, n_frames,
+                                   n_bins, x.shape[-1], _ptr(lengths) if B else None, _ptr(desc) if B else None, flags,
+                                   value, _ptr(fills) if fills.size else None))
+    return (out, fills) if flags & SPECAUG_FILL_MEAN else out
+
+
+def spec_augment(feats, frame_lengths, rows, fill=0.0, freq_major=False, warp=True, out=None, n_cols=None, stream=None):
+    """The device call (mp3g_specaug_rows): as spec_augment_host states it and
+    bit for bit, from the contiguous float32 device tensor feats into `out`
+    (another tensor like it; made here when None).  rows: a host array of
+    SPECAUG_ROW_DTYPE [B], or a uint8 or int32 device tensor of B x 176 bytes.
+    frame_lengths as for cmvn.  out=feats works in place and is allowed only
+    with warp=False: then only the masked words are written.  One launch, two
+    with fill="mean", asynchronous on `stream` (a hipStream_t; None = the
+    current torch stream).  Returns out, or (out, fills) with "mean"."""
+    import torch
+    B, planes, lengths, live = _device_feats("spec_augment", feats, frame_lengths, n_cols)
+    flags, value = _specaug_flags("spec_augment", fill, freq_major, warp)
+    if torch.is_tensor(rows):
+        if (not rows.is_cuda or rows.device != feats.device or rows.dtype not in (torch.uint8, torch.int32)
+                or not rows.is_contiguous() or rows.numel() * rows.element_size() != B * SPECAUG_ROW_DTYPE.itemsize):
+            raise ValueError("spec_augment: rows is a contiguous uint8 or int32 device tensor of B x 176 bytes")
+        d_rows = rows
+    else:
+        desc = np.ascontiguousarray(rows, dtype=SPECAUG_ROW_DTYPE)
+        if desc.shape != (B,):
+            raise ValueError("spec_augment: one descriptor per row")
+        d_rows = torch.from_numpy(desc.view(np.uint8).copy()).to(feats.device)
+    if out is feats and warp:
+        raise ValueError("spec_augment: out=feats needs warp=False (the warp is out of place)")
+    if out is None:
+        out = feats.clone() if live < int(feats.shape[-1]) else torch.empty_like(feats)
+    if (not torch.is_tensor(out) or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != feats.shape
+            or out.device != feats.device):
+        raise ValueError("spec_augment: out is a contiguous float32 tensor like feats")
+    n_frames, n_bins = (live, int(feats.shape[-2])) if freq_major else (int(feats.shape[-2]), live)
+    fills = None
+    if flags & SPECAUG_FILL_MEAN:
+        fills = torch.empty(tuple(feats.shape[:-2]), dtype=torch.float32, device=feats.device)
+    _check(lib().mp3g_specaug_rows(feats.device.index or 0, _dptr(feats), _dptr(out), B, planes, n_frames, n_bins,
+                                   int(feats.shape[-1]), _dptr(lengths), _dptr(d_rows), flags, value,
+                                   _dptr(fills) if fills is not None else None, _stream_of(feats, stream)))
+    return (out, fills) if fills is not None else out
+
+
+def spec_augment_rows(rng, frame_lengths, n_bins, time_warp=0, n_freq_masks=2, freq_mask_width=27, n_time_masks=2,
+                      time_mask_width=100, time_mask_ratio=None):
+    """Draws one SpecAugment descriptor per row from rng (a
+    numpy.random.Generator) and returns the SPECAUG_ROW_DTYPE array [B] that
+    spec_augment takes.  Pure numpy.  Per row of n = frame_lengths[b] frames:
+
+    warp, as ESPnet's time_warp draws it with window W = time_warp: none when
+    W = 0 or n - W <= W; otherwise the centre c uniform in [W, n - W) and its
+    destination w uniform in [c - W + 1, c + W];
+    n_freq_masks frequency masks: width uniform in [0, freq_mask_width] (at
+    most n_bins), start uniform in [0, n_bins - width];
+    n_time_masks time masks: width uniform in [0, T], T = time_mask_width,
+    capped at floor(time_mask_ratio * n) when a ratio is given (the paper's p,
+    ESPnet's ratio range) and at n; start uniform in [0, n - width].  Time masks
+    are drawn against n: the warp leaves the length unchanged.
+
+    The LibriSpeech policies of Park et al. 2019 as parameter sets:
+      LB: time_warp=80, freq_mask_width=27, n_freq_masks=1, time_mask_width=100, n_time_masks=1, time_mask_ratio=1.0
+      LD: time_warp=80, freq_mask_width=27, n_freq_masks=2, time_mask_width=100, n_time_masks=2, time_mask_ratio=1.0
+    and Switchboard's
+      SM: time_warp=40, freq_mask_width=15, n_freq_masks=2, time_mask_width=70, n_time_masks=2, time_mask_ratio=0.2
+      SS: time_warp=40, freq_mask_width=27, n_freq_masks=2, time_mask_width=70, n_time_masks=2, time_mask_ratio=0.2
+    icefall's default is n_time_masks=10 with time_mask_ratio=0.2 shared among
+    them; here the ratio caps each mask."""
+    lengths = np.asarray(frame_lengths, dtype=np.int64).reshape(-1)
+    n_bins, W = int(n_bins), int(time_warp)
+    n_f, n_t = int(n_freq_masks), int(n_time_masks)
+    if not 0 <= n_f <= SPECAUG_MAX_FREQ_MASKS or not 0 <= n_t <= SPECAUG_MAX_TIME_MASKS:
+        raise ValueError("spec_augment_rows: at most %d frequency and %d time masks"
+                         % (SPECAUG_MAX_FREQ_MASKS, SPECAUG_MAX_TIME_MASKS))
+    if n_bins < 0 or W < 0 or int(freq_mask_width) < 0 or int(time_mask_width) < 0 or (lengths < 0).any():
+        raise ValueError("spec_augment_rows: negative count or width")
+    rows = np.zeros(len(lengths), SPECAUG_ROW_DTYPE)
+    for b, n in enumerate(lengths):
+        n = int(min(n, 2 ** 32 - 1))
+        r = rows[b]
+        if W > 0 and n - W > W:
+            c = int(rng.integers(W, n - W))
+            r["warp_center"], r["warp_to"] = c, int(rng.integers(c - W + 1, c + W + 1))
+        r["n_freq"], r["n_time"] = n_f, n_t
+        fmax = min(int(freq_mask_width), n_bins)
+        for k in range(n_f):
+            width = int(rng.integers(0, fmax + 1))
+            r["freq"][k] = (int(rng.integers(0, n_bins - width + 1)), width)
+        tmax = min(int(time_mask_width), n)
+        if time_mask_ratio is not None:
+            tmax = min(tmax, int(float(time_mask_ratio) * n))
+        for k in range(n_t):
+            width = int(rng.integers(0, tmax + 1))
+            r["time"][k] = (int(rng.integers(0, n - width + 1)), width)
+    return rows
+
+
+_spec_augment = spec_augment  # (the decode_windows_*_tensor calls have a parameter of that name)
+
+
+def _specaug_after(name, feats, flen, spec, n_bins, freq_major):
+    """The spec_augment= keyword of a decode_windows_*_tensor call: spec is a
+    descriptor array [B], or a dict of spec_augment_rows' options plus `rng` and
+    `fill`, whose rows are drawn from the call's own frame lengths.  Returns the
+    augmented tensor."""
+    fill = 0.0
+    if isinstance(spec, dict):
+        opts = dict(spec)
+        fill = opts.pop("fill", 0.0)
+        rng = opts.pop("rng", None)
+        if rng is None:
+            raise Mp3gError(1, name + ": spec_augment as a dict needs rng, a numpy.random.Generator")
+        try:
+            rows = spec_augment_rows(rng, flen, n_bins, **opts)
+        except (TypeError, ValueError) as e:
+            raise Mp3gError(1, name + ": spec_augment: " + str(e))
+    else:
+        rows = np.ascontiguousarray(spec, dtype=SPECAUG_ROW_DTYPE)
+        if rows.shape != (len(flen),):
+            raise Mp3gError(1, name + ": spec_augment is one descriptor per stream")
+    out = _spec_augment(feats, flen, rows, fill=fill, freq_major=freq_major, warp=True)
+    return out[0] if isinstance(out, tuple) else out
 
 
 def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_length_ms=25.0, frame_shift_ms=10.0,
@@ -2728,7 +2920,7 @@ class STFT:
 def decode_windows_stft_tensor(datas, starts, n_samples, rate, n_fft=2048, hop=512, win_length=None, output="power",
                                n_mels=0, fmin=0.0, fmax=0.0, htk=False, norm=True, log=None, floor=None, center=True,
                                n_frames=None, mode=MODE_EXACT, out_format=OUT_F32_MONO, gapless=False, quality="fast",
-                               n_threads=0, device=0, speed=None, gain=None):
+                               n_threads=0, device=0, speed=None, gain=None, spec_augment=None):
     """decode_windows_resampled_tensor followed by one STFT.execute on the same
     torch stream: the spectrogram (or mel spectrogram) of each stream's window
     [starts[k], starts[k] + n_samples) at `rate`, zero padding included.  F =
@@ -2744,8 +2936,14 @@ def decode_windows_stft_tensor(datas, starts, n_samples, rate, n_fft=2048, hop=5
 
     speed, gain: speed and volume perturbation before everything else, one
     entry per stream each (decode_windows_resampled_tensor); starts and
-    n_samples then count samples of the perturbed signal."""
+    n_samples then count samples of the perturbed signal.
+
+    spec_augment: None, or SpecAugment of the float32 features in the
+    frequency-major layout (spec_augment with freq_major=True) on the same
+    stream, as for decode_windows_logmel_tensor; complex output is refused."""
     import torch
+    if spec_augment is not None and output == "complex":
+        raise Mp3gError(1, "decode_windows_stft_tensor: spec_augment needs a float32 output, not 'complex'")
     st = STFT(rate, n_fft, hop, win_length, output, n_mels, fmin, fmax, htk, norm, log, floor, center, device=device)
     try:
         T = int(n_samples)
@@ -2757,10 +2955,13 @@ def decode_windows_stft_tensor(datas, starts, n_samples, rate, n_fft=2048, hop=5
             datas, starts, T, rate, mode=mode, out_format=out_format, gapless=gapless, quality=quality,
             n_threads=n_threads, device=device, speed=speed, gain=gain)
         feats = st.execute(batch, n_frames=F)
+        flen = np.minimum(F, -(-lengths // st.hop))
+        if spec_augment is not None:
+            feats = _specaug_after("decode_windows_stft_tensor", feats, flen, spec_augment, int(feats.shape[-2]), True)
         torch.cuda.current_stream(feats.device).synchronize()
     finally:
         st.close()
-    return feats, np.minimum(F, -(-lengths // st.hop)), end_status, rates
+    return feats, flen, end_status, rates
 
 
 def _host_buffer(out, want_int16, want_float32=False):

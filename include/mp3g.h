@@ -1081,6 +1081,96 @@ int mp3g_select_frames_host(const float* in, uint32_t n_rows, uint32_t n_planes,
                             uint32_t n_cols, const uint8_t* voiced, const uint32_t* lengths, float* out,
                             uint32_t n_frames_out, uint32_t stride_out, uint32_t* lengths_out);
 
+/* ---- SpecAugment: time warp, frequency and time masks ---------------------------
+ * The augmentation the ASR recipes apply to the features (Park et al. 2019;
+ * ESPnet's SpecAug, lhotse's and icefall's SpecAugment, wenet's spec_aug,
+ * torchaudio's TimeMasking and FrequencyMasking) on a feature tensor of either
+ * layout:
+ *   time-major, float [n_rows][n_planes][n_frames][stride] with n_bins <= stride
+ *   live columns: the output of mp3g_fbank_execute or mp3g_mfcc_execute;
+ *   with MP3G_SPECAUG_FREQ_MAJOR, float [n_rows][n_planes][n_bins][stride] with
+ *   n_frames <= stride live frames: the output of mp3g_logmel_execute or the mel
+ *   output of mp3g_stft_execute.
+ * lengths: uint32 [n_rows], one frame count per row as for mp3g_cmvn_rows; below,
+ * n = min(lengths[r], n_frames).  The random parameters are the caller's: one
+ * mp3g_specaug_row per row (176 bytes; both planes of a row share it), which the
+ * _rows call reads from device memory, so no launch shape depends on them.
+ *
+ * Nothing in a descriptor can make a call fail.  A mask [start, start + width) is
+ * clipped to [0, n) (time) or [0, n_bins) (frequency), the end formed in 64 bits:
+ * a width of 0 or a start at or past the end masks nothing.  n_time above
+ * MP3G_SPECAUG_MAX_TIME_MASKS (16) and n_freq above MP3G_SPECAUG_MAX_FREQ_MASKS
+ * (4) count as the maxima.  A warp with warp_center or warp_to outside [1, n - 1]
+ * is no warp.
+ *
+ * Order: first the warp, then the union of all masks; time masks count frames
+ * AFTER the warp.  Every mask of a (row, plane) writes the same fill, so the order
+ * among masks does not matter.
+ *
+ * Time warp (MP3G_SPECAUG_WARP; ESPnet's and lhotse's time_warp): with c =
+ * warp_center and w = warp_to, source frames [0, c) are stretched onto
+ * destination frames [0, w) and [c, n) onto [w, n), each segment on its own by
+ * what torch.nn.functional.interpolate(mode="bicubic", align_corners=False)
+ * computes when the other axis keeps its size: a 4-tap cubic convolution along
+ * time with A = -0.75.  The position is stated in integers.  For a segment of
+ * n_in source frames mapped onto n_out destination frames, destination frame j of
+ * the segment:
+ *   p = (2 j + 1) n_in - n_out, in signed 64 bits
+ *   i = floor(p / (2 n_out)), which is >= -1;  r = p - i * 2 n_out
+ *   t = (float)r / (float)(2 n_out), one float32 division of two exact operands
+ *   (n_frames <= 2^22)
+ *   c1(x) = fmaf(fmaf(1.25f, x, -2.25f), x * x, 1.0f), x * x rounded
+ *   c2(x) = fmaf(fmaf(fmaf(-0.75f, x, 3.75f), x, -6.0f), x, 3.0f)
+ *   w0 = c2(t + 1.0f), w1 = c1(t), w2 = c1(1.0f - t), w3 = c2(2.0f - t)
+ *   x0 .. x3 = source frames i - 1 .. i + 2, each clamped to [0, n_in - 1] OF ITS
+ *   OWN SEGMENT
+ *   y = fmaf(w3, x3, fmaf(w2, x2, fmaf(w1, x1, w0 * x0)))
+ * A segment with n_in == n_out has t = 0 and weights 0, 1, 0, 0: it reproduces
+ * its input's values (a -0 may come out as +0).  A row without a warp is copied,
+ * not interpolated: -0 and any NaN payload survive.
+ *
+ * Fill: fill_value, written as given; or with MP3G_SPECAUG_FILL_MEAN the mean of
+ * the row's live region of the INPUT, per plane, in one written-down order that
+ * is the same for both layouts:
+ *   s[f] = the float64 sum of (double)x[f][b] over b ascending from +0.0, f < n
+ *   total = the blocked sum of s[0..n), exactly P[n] of the sliding-window CMN
+ *   above with K = 32
+ *   fill = (float)(total / ((double)n * (double)n_bins));  n = 0: +0.0
+ * The fills are also written to fills, float [n_rows][n_planes], which the caller
+ * provides; the buffer is required with this flag.
+ *
+ * Frames f >= n have their live words copied from in; words at columns or frames
+ * past the live count are never written.  With MP3G_SPECAUG_WARP the call is out
+ * of place and out must not overlap in.  Without it the warp fields are ignored
+ * and out == in exactly is allowed: only the masked words are then written, and
+ * no other word is read or written.  A partial overlap is refused.  A stride
+ * below the live count, an unknown flag, a null pointer with work to do or a bad
+ * overlap is MP3G_ERR_INVALID_ARGUMENT before any device call; n_frames above
+ * 2^22 with the warp flag is MP3G_ERR_UNSUPPORTED; no rows, planes, frames or
+ * bins is MP3G_OK with nothing done (with FILL_MEAN the fills are written, +0.0).
+ * mp3g_specaug_rows: device pointers throughout; one launch, or two with
+ * FILL_MEAN (the sums first), whose shapes depend on no buffer's contents,
+ * asynchronous on hip_stream; the library allocates nothing.  Its output, the
+ * fills included, equals mp3g_specaug_host's bit for bit. */
+#define MP3G_SPECAUG_FREQ_MAJOR 1u
+#define MP3G_SPECAUG_WARP 2u
+#define MP3G_SPECAUG_FILL_MEAN 4u
+#define MP3G_SPECAUG_MAX_TIME_MASKS 16
+#define MP3G_SPECAUG_MAX_FREQ_MASKS 4
+typedef struct mp3g_specaug_row {
+  uint32_t warp_center, warp_to; /* frames [0,c) -> [0,w), [c,n) -> [w,n); see above */
+  uint32_t n_time, n_freq;       /* masks in use; values above the maxima count as the maxima */
+  uint32_t time[MP3G_SPECAUG_MAX_TIME_MASKS][2]; /* start, width, in frames AFTER the warp */
+  uint32_t freq[MP3G_SPECAUG_MAX_FREQ_MASKS][2]; /* start, width, in bins */
+} mp3g_specaug_row;
+int mp3g_specaug_rows(int device, const float* d_in, float* d_out, uint32_t n_rows, uint32_t n_planes,
+                      uint32_t n_frames, uint32_t n_bins, uint32_t stride, const uint32_t* d_lengths,
+                      const mp3g_specaug_row* d_desc, uint32_t flags, float fill_value, float* d_fill,
+                      void* hip_stream);
+int mp3g_specaug_host(const float* in, float* out, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames,
+                      uint32_t n_bins, uint32_t stride, const uint32_t* lengths, const mp3g_specaug_row* desc,
+                      uint32_t flags, float fill_value, float* fills);
+
 /* ---- Integrated loudness of decoded rows ----------------------------------------
  * ITU-R BS.1770-4 integrated loudness (what libebur128, pyloudnorm and ffmpeg's
  * loudnorm report as "I") and the sample peak of every row of a batch
