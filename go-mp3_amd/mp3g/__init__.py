@@ -215,6 +215,14 @@ def lib():
         if hasattr(L, "mp3g_specaug_rows"):
             L.mp3g_specaug_rows.argtypes = [C.c_int, vp, vp, u32, u32, u32, u32, u32, vp, vp, u32, C.c_float, vp, vp]
             L.mp3g_specaug_host.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, vp, u32, C.c_float, vp]
+        if hasattr(L, "mp3g_add_deltas_rows"):
+            L.mp3g_delta_scales.argtypes = [u32, u32, vp]
+            L.mp3g_add_deltas_rows.argtypes = [C.c_int, vp, vp] + [u32] * 6 + [vp, u32, u32, u32, vp]
+            L.mp3g_add_deltas_host.argtypes = [vp, vp] + [u32] * 6 + [vp, u32, u32, u32]
+            L.mp3g_stack_frames_count.argtypes = [u32, u32, u32]
+            L.mp3g_stack_frames_count.restype = u32
+            L.mp3g_stack_frames_rows.argtypes = [C.c_int, vp] + [u32] * 5 + [vp] + [u32] * 5 + [vp, u32, u32, vp, vp]
+            L.mp3g_stack_frames_host.argtypes = [vp] + [u32] * 5 + [vp] + [u32] * 5 + [vp, u32, u32, vp]
         if hasattr(L, "mp3g_loudness_create"):
             dp = C.POINTER(vp)
             L.mp3g_loudness_create.argtypes = [C.c_int, C.c_int, dp]
@@ -1375,7 +1383,7 @@ def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_leng
                                 n_mels=80, low_freq=20.0, high_freq=0.0, preemphasis=0.97, remove_dc=True,
                                 window="povey", snip_edges=True, scale=32768.0, n_frames=None, mode=MODE_EXACT,
                                 out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0, device=0,
-                                speed=None, gain=None, cmvn=None, spec_augment=None):
+                                speed=None, gain=None, cmvn=None, spec_augment=None, deltas=None, stack=None):
     """decode_windows_resampled_tensor followed by FBank.execute on the same
     torch stream: Kaldi's filter-bank features of each stream's window
     [starts[k], starts[k] + n_samples) at `rate`, zero padding included.
@@ -1399,10 +1407,17 @@ def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_leng
     (normalised) features (spec_augment, time-major) on the same stream: a
     descriptor array [B], or a dict of spec_augment_rows' options plus `rng`
     and `fill`, whose rows are drawn from the returned frame_lengths.  The
-    recipes normalise before they mask: a fill of 0 is then the mean."""
+    recipes normalise before they mask: a fill of 0 is then the mean.
+
+    deltas: None or dict(order=, window=): add_deltas of the result, n_mels *
+    (order + 1) columns.  stack: None or dict(left=, right=, step=, first=)
+    (lfr_options(7, 6) is the Paraformer front end): stack_frames after that;
+    the features then have stack_frames_count(F, step, first) frames and the
+    returned frame_lengths are the stacked counts.  Both on the same stream."""
     import torch
     if cmvn not in CMVN_MODES:
         raise Mp3gError(1, "decode_windows_fbank_tensor: cmvn is None, 'mean' or 'mean_var'")
+    _framectx_options("decode_windows_fbank_tensor", deltas, stack)
     fb = FBank(rate, frame_length_ms, frame_shift_ms, n_mels, low_freq, high_freq, preemphasis, remove_dc, window,
                snip_edges, scale, device=device)
     try:
@@ -1424,6 +1439,8 @@ def decode_windows_fbank_tensor(datas, starts, n_samples, rate=16000, frame_leng
             _cmvn_rows(feats, flen, norm_vars=CMVN_MODES[cmvn])
         if spec_augment is not None:
             feats = _specaug_after("decode_windows_fbank_tensor", feats, flen, spec_augment, fb.n_mels, False)
+        if deltas is not None or stack is not None:
+            feats, flen = _framectx_after(feats, flen, deltas, stack)
         torch.cuda.current_stream(feats.device).synchronize()
     finally:
         fb.close()
@@ -1953,13 +1970,216 @@ def _specaug_after(name, feats, flen, spec, n_bins, freq_major):
     return out[0] if isinstance(out, tuple) else out
 
 
+# ---- delta features and frame context (include/mp3g.h) ----------------------------
+DELTA_OPTIONS = ("order", "window")
+STACK_OPTIONS = ("left", "right", "step", "first")
+DELTA_MAX_ORDER = 4
+DELTA_MAX_HALO = 32
+STACK_MAX_CONTEXT = 64
+
+
+def _plane_lengths_host(name, frame_lengths, B, planes):
+    """(lengths uint32 C-order, len_planes) of frame_lengths [B] or [B, planes]."""
+    lengths = np.ascontiguousarray(np.minimum(np.asarray(frame_lengths, dtype=np.int64), 2 ** 32 - 1), dtype=np.uint32)
+    if lengths.shape == (B,):
+        return lengths, 1
+    if lengths.shape == (B, planes):
+        return lengths, planes
+    raise ValueError(name + ": frame_lengths is [B] or [B, planes]")
+
+
+def _plane_lengths_device(name, frame_lengths, B, planes, device):
+    """(lengths int32 device tensor, len_planes) of frame_lengths [B] or [B, planes], host or device."""
+    import torch
+    if torch.is_tensor(frame_lengths) and frame_lengths.is_cuda:
+        lengths = frame_lengths.to(torch.int32).contiguous()
+    else:
+        host = np.ascontiguousarray(np.minimum(np.asarray(frame_lengths, dtype=np.int64), 2 ** 31 - 1), dtype=np.int32)
+        lengths = torch.from_numpy(host).to(device)
+    if tuple(lengths.shape) == (B,):
+        return lengths, 1
+    if tuple(lengths.shape) == (B, planes):
+        return lengths, planes
+    raise ValueError(name + ": frame_lengths is [B] or [B, planes]")
+
+
+def _host_tensor(name, feats, n_cols):
+    """(x float32 C-order [B, (C,) F, S], B, planes, cols) of a host call."""
+    x = np.ascontiguousarray(feats, dtype=np.float32)
+    if x.ndim not in (3, 4):
+        raise ValueError(name + ": feats is [B, F, S] or [B, C, F, S]")
+    return x, x.shape[0], (x.shape[1] if x.ndim == 4 else 1), (x.shape[-1] if n_cols is None else int(n_cols))
+
+
+def _device_tensor(name, feats, n_cols):
+    """(B, planes, cols) of a device call on feats."""
+    import torch
+    if (not torch.is_tensor(feats) or feats.dtype != torch.float32 or not feats.is_contiguous() or not feats.is_cuda
+            or feats.dim() not in (3, 4)):
+        raise ValueError(name + ": a contiguous float32 device tensor [B, F, S] or [B, C, F, S]")
+    return (int(feats.shape[0]), (int(feats.shape[1]) if feats.dim() == 4 else 1),
+            (int(feats.shape[-1]) if n_cols is None else int(n_cols)))
+
+
+def _host_out(name, out, lead, frames, width):
+    """The array a host call writes: zeros [lead.., frames, width], or a copy of `out`
+    [lead.., frames or any, S_out] whose other words are kept."""
+    if out is None:
+        return np.zeros(tuple(lead) + (frames, width), np.float32)
+    y = np.array(out, dtype=np.float32, order="C", copy=True)
+    if y.ndim != len(lead) + 2 or y.shape[:-2] != tuple(lead):
+        raise ValueError(name + ": out is [B, (C,) frames, S_out]")
+    return y
+
+
+def _device_out(name, out, feats, frames, width):
+    """The tensor a device call writes: made here when None (of exactly the live
+    width), else a contiguous float32 tensor [B, (C,) frames, S_out]."""
+    import torch
+    if out is None:
+        out = torch.empty(tuple(feats.shape[:-2]) + (frames, width), dtype=torch.float32, device=feats.device)
+    if (not torch.is_tensor(out) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != feats.device
+            or out.dim() != feats.dim() or out.shape[:-2] != feats.shape[:-2]):
+        raise ValueError(name + ": out is a contiguous float32 device tensor [B, (C,) frames, S_out]")
+    return out
+
+
+def delta_scales(order, window):
+    """Kaldi's delta scales in float32 (mp3g_delta_scales): a list of order + 1
+    arrays, the i-th of 2 * i * window + 1 taps; [array([1.])] for order 0.  Order
+    i is made from the already rounded order i - 1."""
+    order, window = int(order), int(window)
+    sizes = [2 * i * window + 1 for i in range(order + 1)]
+    buf = np.zeros(max(1, sum(sizes)) if 0 <= order <= DELTA_MAX_ORDER and 0 < window <= DELTA_MAX_HALO else 1,
+                   np.float32)
+    _check(lib().mp3g_delta_scales(order, window, _ptr(buf)))
+    return [a.copy() for a in np.split(buf, np.cumsum(sizes)[:-1])]
+
+
+def add_deltas_host(feats, frame_lengths, order=2, window=2, n_cols=None, out=None):
+    """The reference on the CPU (mp3g_add_deltas_host; Kaldi's add-deltas): the
+    float32 array [B, (C,) F, (order + 1) * n_cols] whose block 0 is a bit copy
+    of feats' columns below n_cols (all S by default) and whose block i is the
+    i-th order delta -- fmaf over delta_scales(order, window)[i], the neighbours
+    clamped to the row's first min(frame_lengths, F) frames, every order on the
+    original frames.  Frames past the length are +0.  frame_lengths: [B], or
+    [B, C] with one count per plane.  `out`, when given, is an array [B, (C,) F,
+    S_out] whose other words are kept (a copy is returned)."""
+    x, B, planes, cols = _host_tensor("add_deltas_host", feats, n_cols)
+    lengths, lp = _plane_lengths_host("add_deltas_host", frame_lengths, B, planes)
+    order, window = int(order), int(window)
+    y = _host_out("add_deltas_host", out, x.shape[:-2], x.shape[-2], (max(order, 0) + 1) * cols)
+    if y.shape[-2] != x.shape[-2]:
+        raise ValueError("add_deltas_host: out has feats' frames")
+    _check(lib().mp3g_add_deltas_host(_ptr(x) if x.size else None, _ptr(y) if y.size else None, B, planes, x.shape[-2],
+                                      x.shape[-1], cols, y.shape[-1], _ptr(lengths) if B else None, lp, order, window))
+    return y
+
+
+def add_deltas(feats, frame_lengths, order=2, window=2, out=None, n_cols=None, stream=None):
+    """The device call (mp3g_add_deltas_rows): as add_deltas_host states it and
+    bit for bit, from the contiguous float32 device tensor feats [B, (C,) F, S]
+    into `out` [B, (C,) F, S_out], S_out >= (order + 1) * n_cols (made here when
+    None, with exactly that width).  frame_lengths: [B] or [B, C], anything
+    array-like or an int32 device tensor.  One launch, asynchronous on `stream`
+    (a hipStream_t; None = the current torch stream).  Returns out."""
+    B, planes, cols = _device_tensor("add_deltas", feats, n_cols)
+    lengths, lp = _plane_lengths_device("add_deltas", frame_lengths, B, planes, feats.device)
+    order, window = int(order), int(window)
+    width = (max(order, 0) + 1) * cols
+    out = _device_out("add_deltas", out, feats, int(feats.shape[-2]), width)
+    if out.shape[-2] != feats.shape[-2]:
+        raise ValueError("add_deltas: out has feats' frames")
+    _check(lib().mp3g_add_deltas_rows(feats.device.index or 0, _dptr(feats), _dptr(out), B, planes,
+                                      int(feats.shape[-2]), int(feats.shape[-1]), cols, int(out.shape[-1]),
+                                      _dptr(lengths), lp, order, window, _stream_of(feats, stream)))
+    return out
+
+
+def stack_frames_count(n_frames, step=1, first=0):
+    """The frames a stack leaves of n_frames (mp3g_stack_frames_count): 0 when
+    n_frames <= first, else ceil((n_frames - first) / step)."""
+    return int(lib().mp3g_stack_frames_count(int(n_frames), int(step), int(first)))
+
+
+def lfr_options(m=7, n=6):
+    """The stack parameters of FunASR's apply_lfr(m, n): m frames stacked at a
+    stride of n, the first padded on the left with frame 0, the last repeated."""
+    left = (int(m) - 1) // 2
+    return dict(left=left, right=int(m) - 1 - left, step=int(n), first=0)
+
+
+def stack_frames_host(feats, frame_lengths, left=0, right=0, step=1, first=0, n_frames_out=None, n_cols=None, out=None):
+    """The reference on the CPU (mp3g_stack_frames_host): (out float32 [B, (C,)
+    n_frames_out, (left + right + 1) * n_cols], lengths_out int32 [B, (C)]).
+    Output frame j of a row of n = min(frame_lengths, F) frames has the anchor
+    t = first + j * step and is the bit copy of frames t - left .. t + right,
+    each clamped to [0, n - 1], side by side; there are lengths_out =
+    min(stack_frames_count(n, step, first), n_frames_out) of them and the frames
+    after them are +0.  splice-feats is (L, R, 1, 0), apply_lfr lfr_options(m,
+    n), subsample-feats (0, 0, N, offset).  n_frames_out: stack_frames_count(F,
+    step, first) by default.  frame_lengths: [B] or [B, C].  `out`, when given,
+    is an array [B, (C,) n_frames_out, S_out] whose other words are kept (a copy
+    is returned)."""
+    x, B, planes, cols = _host_tensor("stack_frames_host", feats, n_cols)
+    lengths, lp = _plane_lengths_host("stack_frames_host", frame_lengths, B, planes)
+    left, right, step, first = int(left), int(right), int(step), int(first)
+    Fo = stack_frames_count(x.shape[-2], step, first) if n_frames_out is None else int(n_frames_out)
+    y = _host_out("stack_frames_host", out, x.shape[:-2], Fo, (max(left, 0) + max(right, 0) + 1) * cols)
+    m = np.zeros(x.shape[:-2], np.uint32)
+    _check(lib().mp3g_stack_frames_host(_ptr(x) if x.size else None, B, planes, x.shape[-2], x.shape[-1], cols,
+                                        _ptr(lengths) if B else None, lp, left, right, step, first,
+                                        _ptr(y) if y.size else None, y.shape[-2], y.shape[-1],
+                                        _ptr(m) if m.size else None))
+    return y, m.astype(np.int32)
+
+
+def stack_frames(feats, frame_lengths, left=0, right=0, step=1, first=0, n_frames_out=None, n_cols=None, out=None,
+                 stream=None):
+    """The device call (mp3g_stack_frames_rows): as stack_frames_host states it
+    and bit for bit, from the contiguous float32 device tensor feats into `out`
+    [B, (C,) n_frames_out, S_out] (made here when None).  No frame count is read
+    back: the output keeps its static shape.  Returns (out, lengths_out int32
+    [B, (C)]).  One launch, asynchronous on `stream`."""
+    import torch
+    B, planes, cols = _device_tensor("stack_frames", feats, n_cols)
+    lengths, lp = _plane_lengths_device("stack_frames", frame_lengths, B, planes, feats.device)
+    left, right, step, first = int(left), int(right), int(step), int(first)
+    Fo = stack_frames_count(int(feats.shape[-2]), step, first) if n_frames_out is None else int(n_frames_out)
+    width = (max(left, 0) + max(right, 0) + 1) * cols
+    out = _device_out("stack_frames", out, feats, Fo, width)
+    m = torch.empty(tuple(feats.shape[:-2]), dtype=torch.int32, device=feats.device)
+    _check(lib().mp3g_stack_frames_rows(feats.device.index or 0, _dptr(feats), B, planes, int(feats.shape[-2]),
+                                        int(feats.shape[-1]), cols, _dptr(lengths), lp, left, right, step, first,
+                                        _dptr(out), int(out.shape[-2]), int(out.shape[-1]), _dptr(m),
+                                        _stream_of(feats, stream)))
+    return out, m
+
+
+def _framectx_options(name, deltas, stack):
+    """The deltas= and stack= keywords of a decode_windows_*_tensor call, checked before any work."""
+    for key, value, allowed in (("deltas", deltas, DELTA_OPTIONS), ("stack", stack, STACK_OPTIONS)):
+        if value is not None and (not isinstance(value, dict) or set(value) - set(allowed)):
+            raise Mp3gError(1, "%s: %s is None or a dict of %s" % (name, key, ", ".join(allowed)))
+
+
+def _framectx_after(feats, flen, deltas, stack):
+    """deltas, then stack, of the features on the current stream.  Returns (feats, frame_lengths)."""
+    if deltas is not None:
+        feats = add_deltas(feats, flen, **deltas)
+    if stack is not None:
+        feats, counts = stack_frames(feats, flen, **stack)
+        flen = counts.cpu().numpy().astype(np.int64)  # (the copy waits for the stream)
+    return feats, flen
+
+
 def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_length_ms=25.0, frame_shift_ms=10.0,
                                n_mels=23, n_ceps=13, cepstral_lifter=22.0, use_energy=True, raw_energy=True,
                                energy_floor=0.0, low_freq=20.0, high_freq=0.0, preemphasis=0.97, remove_dc=True,
                                window="povey", snip_edges=True, scale=32768.0, cmvn=None, n_frames=None,
                                mode=MODE_EXACT, out_format=OUT_F32_MONO, gapless=False, quality="fast", n_threads=0,
                                device=0, cmn_window=300, min_cmn_window=100, center=True, vad=None,
-                               speed=None, gain=None):
+                               speed=None, gain=None, deltas=None, stack=None):
     """decode_windows_resampled_tensor, MFCC.execute and, with cmvn = "mean"
     or "mean_var", the per-row normalisation over each stream's own frames, all
     on the current torch stream: Kaldi's MFCC features of each stream's window
@@ -1985,10 +2205,18 @@ def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_lengt
 
     speed, gain: speed and volume perturbation before everything else, one
     entry per stream each (decode_windows_resampled_tensor); starts and
-    n_samples then count samples of the perturbed signal."""
+    n_samples then count samples of the perturbed signal.
+
+    deltas: None or dict(order=, window=): add_deltas after the selection (the
+    GMM recipes' apply-cmvn | add-deltas), n_ceps * (order + 1) columns.  stack:
+    None or dict(left=, right=, step=, first=): stack_frames after that (the
+    TDNN recipes' splice-feats; subsampling); the features then have
+    stack_frames_count(F, step, first) frames and the returned frame_lengths are
+    the stacked counts.  Both take the voiced counts per plane as they are."""
     import torch
     if cmvn not in CMVN_MODES and cmvn not in SLIDING_CMVN_MODES:
         raise Mp3gError(1, "decode_windows_mfcc_tensor: cmvn is None, 'mean', 'mean_var', 'sliding' or 'sliding_var'")
+    _framectx_options("decode_windows_mfcc_tensor", deltas, stack)
     if vad is not None:
         if not isinstance(vad, dict) or set(vad) - set(VAD_OPTIONS):
             raise Mp3gError(1, "decode_windows_mfcc_tensor: vad is None or a dict of " + ", ".join(VAD_OPTIONS))
@@ -2020,6 +2248,8 @@ def decode_windows_mfcc_tensor(datas, starts, n_samples, rate=16000, frame_lengt
         if vad is not None:
             feats, counts = select_frames(feats, voiced, flen)
             flen = counts.cpu().numpy().astype(np.int64)  # (the copy waits for the stream)
+        if deltas is not None or stack is not None:
+            feats, flen = _framectx_after(feats, flen, deltas, stack)
         torch.cuda.current_stream(feats.device).synchronize()
     finally:
         mf.close()

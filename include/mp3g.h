@@ -66,7 +66,10 @@ extern "C" {
  *    selection of feature tensors -- mp3g_sliding_cmn_*, mp3g_vad_energy_* and
  *    mp3g_select_frames_*; variable-ratio resampling of decoded rows (speed
  *    and volume perturbation) -- mp3g_varresampler_*, mp3g_varresample_host
- *    and mp3g_varresample_rows.) */
+ *    and mp3g_varresample_rows; SpecAugment of feature tensors --
+ *    mp3g_specaug_*; delta features and frame context (splicing,
+ *    low-frame-rate stacking, subsampling) of feature tensors --
+ *    mp3g_delta_scales, mp3g_add_deltas_* and mp3g_stack_frames_*.) */
 #define MP3G_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------ */
@@ -1170,6 +1173,78 @@ int mp3g_specaug_rows(int device, const float* d_in, float* d_out, uint32_t n_ro
 int mp3g_specaug_host(const float* in, float* out, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames,
                       uint32_t n_bins, uint32_t stride, const uint32_t* lengths, const mp3g_specaug_row* desc,
                       uint32_t flags, float fill_value, float* fills);
+
+/* ---- Delta features and frame context --------------------------------------------
+ * The steps that sit between the features and the model in the recipes: Kaldi's
+ * add-deltas, and one gather that is splice-feats, FunASR's low-frame-rate
+ * stacking (apply_lfr) and subsample-feats.  Both work on the time-major tensor
+ * float [n_rows][n_planes][n_frames][stride] of which n_cols <= stride columns are
+ * live: the output of mp3g_fbank_execute or mp3g_mfcc_execute, or of any call of
+ * the three sections above.  lengths: uint32 [n_rows][len_planes], len_planes 1
+ * (one count per row, as for mp3g_cmvn_rows) or n_planes (one per plane: the
+ * lengths_out of mp3g_select_frames_rows as they stand); below, n =
+ * min(lengths[r][p], n_frames).  Both are out of place (out must not overlap in)
+ * and never write a word at a column past the live output width.  Every device
+ * call (*_rows: device pointers throughout) equals its host call bit for bit, is
+ * one launch whose shape depends on no buffer's contents, asynchronous on
+ * hip_stream, and allocates nothing; all offsets are formed in 64 bits.
+ *
+ * Deltas: Kaldi's DeltaFeatures (add-deltas --delta-order=O --delta-window=W), as
+ * stated HERE: this statement, written without Kaldi's source at hand, is the
+ * definition the project tests.  The scales, in float32: scales[0] = {1}; for i =
+ * 1..O, cur has len(prev) + 2 W zeros, and for j = -W..W ascending, then k over
+ * prev ascending, cur[j + k + offset] += (float)j * prev[k] -- a float32 product,
+ * then a float32 add, not fused -- and then every entry is multiplied by
+ * (float)(1.0 / (double)norm), norm = the sum of j^2.  Order 2 is therefore built
+ * from the already rounded order-1 scales.  mp3g_delta_scales writes them, order 0
+ * first, order i as 2 i W + 1 floats: (O + 1) + W O (O + 1) floats in all.
+ * out: float [n_rows][n_planes][n_frames][stride_out], stride_out >= (O + 1) *
+ * n_cols.  For t < n, block 0 (columns [0, n_cols)) is a bit copy of the input
+ * frame: -0 and NaN payloads survive.  Block i >= 1, column c: y = +0.0f; for j =
+ * -i W..i W ascending, a tap whose scale is exactly 0 is skipped (as Kaldi skips
+ * it: 0 * Inf stays out), any other is y = fmaf(scale_i[j], x[clamp(t + j, 0,
+ * n - 1)][c], y).  Every order clamps on the ORIGINAL frames: order 2 is not order
+ * 1 applied twice, and the two differ at a row's edges.  Frames t >= n are +0 in
+ * all (O + 1) * n_cols live columns.  O = 0 is a copy with zero padding.
+ * stride < n_cols, stride_out < (O + 1) * n_cols, W = 0, len_planes neither 1 nor
+ * n_planes, out == in, out overlapping in or a null pointer with work to do is
+ * MP3G_ERR_INVALID_ARGUMENT; O > 4 or O * W > 32 is MP3G_ERR_UNSUPPORTED; all
+ * before any device call.  No rows, planes, frames or columns is MP3G_OK with
+ * nothing done.
+ *
+ * Frame context: parameters left, right <= 64 (above: MP3G_ERR_UNSUPPORTED), step
+ * >= 1 and first.  n_out(n) = 0 if n <= first, else ceil((n - first) / step):
+ * mp3g_stack_frames_count.  out: float [n_rows][n_planes][n_frames_out]
+ * [stride_out], stride_out >= (left + right + 1) * n_cols.  With m = min(n_out(n),
+ * n_frames_out), output frame j < m has the anchor t = first + j * step, and its
+ * block k = 0..left + right, columns [k * n_cols, (k + 1) * n_cols), is a bit copy
+ * of input frame clamp(t - left + k, 0, n - 1); frames m <= j < n_frames_out are
+ * +0 in their live columns; lengths_out (uint32 [n_rows][n_planes]) = m, written
+ * whenever there is a row and a plane.
+ *   splice-feats --left-context=L --right-context=R: left L, right R, step 1, first 0
+ *   FunASR apply_lfr(m, n): left (m - 1) / 2, right m - 1 - left, step n, first 0
+ *     (its left padding with frame 0, ceil(T / n) outputs, the last frame repeated)
+ *   subsample-feats --n=N --offset=o: left 0, right 0, step N, first o
+ * stride < n_cols, stride_out below the live width, step = 0, len_planes neither
+ * 1 nor n_planes, out == in, out overlapping in or a null pointer with work to do
+ * is MP3G_ERR_INVALID_ARGUMENT before any device call. */
+int mp3g_delta_scales(uint32_t order, uint32_t window, float* out);
+int mp3g_add_deltas_rows(int device, const float* d_in, float* d_out, uint32_t n_rows, uint32_t n_planes,
+                         uint32_t n_frames, uint32_t stride, uint32_t n_cols, uint32_t stride_out,
+                         const uint32_t* d_lengths, uint32_t len_planes, uint32_t order, uint32_t window,
+                         void* hip_stream);
+int mp3g_add_deltas_host(const float* in, float* out, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames,
+                         uint32_t stride, uint32_t n_cols, uint32_t stride_out, const uint32_t* lengths,
+                         uint32_t len_planes, uint32_t order, uint32_t window);
+uint32_t mp3g_stack_frames_count(uint32_t n_frames, uint32_t step, uint32_t first);
+int mp3g_stack_frames_rows(int device, const float* d_in, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames,
+                           uint32_t stride, uint32_t n_cols, const uint32_t* d_lengths, uint32_t len_planes,
+                           uint32_t left, uint32_t right, uint32_t step, uint32_t first, float* d_out,
+                           uint32_t n_frames_out, uint32_t stride_out, uint32_t* d_lengths_out, void* hip_stream);
+int mp3g_stack_frames_host(const float* in, uint32_t n_rows, uint32_t n_planes, uint32_t n_frames, uint32_t stride,
+                           uint32_t n_cols, const uint32_t* lengths, uint32_t len_planes, uint32_t left,
+                           uint32_t right, uint32_t step, uint32_t first, float* out, uint32_t n_frames_out,
+                           uint32_t stride_out, uint32_t* lengths_out);
 
 /* ---- Integrated loudness of decoded rows ----------------------------------------
  * ITU-R BS.1770-4 integrated loudness (what libebur128, pyloudnorm and ffmpeg's
